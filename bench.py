@@ -9,11 +9,19 @@ fp32 complex, 1 Rx, 1-D OS-CFAR 16 ref / 4 guard -- in batches of 1024 frames pe
 processes its own 1024 frames (frame sharding, no data-path collective) and the detection
 lists are gathered over RCCL inside the step (config 4).
 
-The same JSON line carries sub-records "config3" and "config5" (BASELINE configs 3 and 5, 16
-frames per GPU per step, 2-D OS-CFAR), timed the same way in the same process, each with the
-roofline of ITS dominant kernel (the kernel with the most time per step).
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, the
+output dump if --dump-outputs is given, and the result line.  With --full the line also carries
+the per-kernel rooflines (a profiled repeat of the timed steps), the H2D-inclusive rate, the CPU
+baseline and the sub-records "config3" and "config5" (BASELINE configs 3 and 5, 16 frames per
+GPU per step, 2-D OS-CFAR), timed the same way in the same process, each with the roofline of
+ITS dominant kernel (the kernel with the most time per step); --no-sub, --no-h2d and
+--no-cpu-baseline drop single parts of a --full run.
 
-Launch: `python bench.py [--gpus N --steps K --warmup W]`, or for N > 1
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy
+(dump_outputs below); the inputs are seeded, so two builds run with the same arguments can be
+compared output for output.
+
+Launch: `python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]`, or for N > 1
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
  --master-port P bench.py --gpus N ...`.  Rank 0 prints ONE JSON line.
 
@@ -22,7 +30,7 @@ has run, the same count on every rank; "warmup_steps_run" reports the total.  Th
 its steady clocks only after ~0.1 s of load, so timing K=10 steps after 3 warm-up steps (4 ms)
 read 7-10 % low (profiles/r04/warmup/).  --prewarm-s 0 restores the W-only warm-up.
 
-roofline: the dominant kernel's algorithmic bytes per launch / its average launch duration,
+roofline (--full): the dominant kernel's algorithmic bytes per launch / its average launch duration,
 from HIP events the library records on the launch stream (fmcw_set_profiling: the dispatches'
 own begin / end timestamps, hipExtLaunchKernelGGL) over a profiled repeat of the timed steps.  traffic: HBM bytes per launch from rocprofv3 PMC passes
 (profiles/pmc_r05.json, per frame x the launch's mean frames; tools/pmc_summary.py), or null.
@@ -67,13 +75,19 @@ def parse():
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
     ap.add_argument("--frames", type=int, default=0, help="frames per GPU per step (0 = workload default)")
     ap.add_argument("--chunk", type=int, default=0, help="frames per kernel chunk (0 = library auto)")
-    ap.add_argument("--no-sub", action="store_true", help="skip the config-3 / config-5 sub-records")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel rooflines (a profiled "
+                         "repeat of the timed steps), the H2D-inclusive rate, the config-3 / config-5 sub-records "
+                         "and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-sub", action="store_true", help="--full: skip the config-3 / config-5 sub-records")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-gather", action="store_true")
     ap.add_argument("--gather", default="rccl", choices=["rccl", "torch"],
                     help="N > 1: libfmcw's RCCL gather-to-root (no host sync) or torch all_gather")
-    ap.add_argument("--no-h2d", action="store_true", help="skip the H2D-inclusive measurement")
+    ap.add_argument("--no-h2d", action="store_true", help="--full: skip the H2D-inclusive measurement")
     ap.add_argument("--spectrum", default=None, choices=["f32", "f16", "s48"],
                     help="element type of the corner-turned spectrum (fmcw.h fmcw_spectrum_dtype); default: "
                          "the workload's (WORKLOADS: s48 at config 2, where A/B measured it faster, f32 at "
@@ -163,6 +177,53 @@ def spectrum_of(wl, args, primary):
     """The corner-turned spectrum format a workload runs: --spectrum for the primary workload if
     given, else the workload's own (WORKLOADS)."""
     return args.spectrum if primary and args.spectrum else wl["spectrum"]
+
+
+DUMP_MAP_BYTES = 32 << 20   # whole frames of the map
+DUMP_CELLS = 1 << 20        # single map cells drawn over the whole batch (4 MB + 8 MB of indices)
+DUMP_DET_ROWS = 1 << 18     # detection records, 5 float64 each (10 MB)
+
+
+def dump_outputs(path, rd_map, dets, status, gathered=None):
+    """--dump-outputs: what the last timed step handed to its caller, as .npy files of at most
+    ~55 MB in all (the config-2 map alone is 1 GiB, so the map is sampled; the sample is drawn
+    from a fixed seed and is the same for every run with the same arguments):
+
+      rd_map_frames.npy       float32 [k][range][doppler]: k whole frames of the map (32 MB at most)
+      rd_map_frame_index.npy  float64 [k]: which frames those are
+      rd_map_cells.npy        float32 [2^20]: single cells drawn over the whole batch's map
+      rd_map_cell_index.npy   float64 [2^20]: their flat indices into [frame][range][doppler]
+      dets.npy                float64 [n][5]: the ordered detection list (frame, range, doppler,
+                              mag, threshold), its first 2^18 records at most
+      status.npy              float64 [4]: the status words (found, lost, window / word saturations)
+      gathered_dets.npy       N > 1, rank 0, RCCL gather: the gathered list, like dets.npy
+    """
+    import numpy as np
+    import torch
+    from fmcw import DET_DTYPE
+
+    d = Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    dev = rd_map.device
+    g = torch.Generator().manual_seed(20240)
+    F = rd_map.shape[0]
+    k = max(1, min(F, DUMP_MAP_BYTES // (rd_map[0].numel() * 4)))
+    fr = torch.randperm(F, generator=g)[:k].sort().values
+    np.save(d / "rd_map_frames.npy", rd_map[fr.to(dev)].cpu().numpy())
+    np.save(d / "rd_map_frame_index.npy", fr.numpy().astype(np.float64))
+    idx = torch.randint(0, rd_map.numel(), (DUMP_CELLS,), generator=g)
+    np.save(d / "rd_map_cells.npy", rd_map.view(-1)[idx.to(dev)].cpu().numpy())
+    np.save(d / "rd_map_cell_index.npy", idx.numpy().astype(np.float64))     # exact: < 2^53
+
+    def records(t, n):
+        r = t[:min(int(n), t.shape[0], DUMP_DET_ROWS)].cpu().numpy().view(DET_DTYPE).reshape(-1)
+        return np.stack([r[f].astype(np.float64) for f in DET_DTYPE.names], axis=1)
+
+    st = status.cpu().numpy().view(np.uint32)
+    np.save(d / "dets.npy", records(dets, st[0]))
+    np.save(d / "status.npy", st.astype(np.float64))
+    if gathered is not None:
+        np.save(d / "gathered_dets.npy", records(gathered[0], gathered[1].cpu().numpy().view(np.uint32)[0]))
 
 
 def run_workload(name, args, world, rank, dev, primary, pmc, n_cu):
@@ -314,16 +375,21 @@ def run_workload(name, args, world, rank, dev, primary, pmc, n_cu):
     elapsed = timed(steps)
     st = n_dets.tolist()
     n_det_step = int(st[0])
+    if primary and args.dump_outputs and rank == 0:
+        d_last, nd_last = bufs[(last["i"] - 1) % 2]           # the buffers of the last timed step
+        dump_outputs(args.dump_outputs, rd_map, d_last, nd_last, (root_out, root_n) if rg is not None else None)
 
-    # profiled repeat: per-kernel durations from HIP events on the launch stream
-    core.reset_kernel_times()
-    core.set_profiling(True)
-    elapsed_prof = timed(steps)
-    kt = core.kernel_times()
-    core.set_profiling(False)
     spectrum = spectrum_of(wl, args, primary)
-    kern = kernel_rooflines(wl, name, F, steps, kt, spectrum, n_cu, pmc)
-    dom = max((k for k in kern if k in ("k_range", "k_doppler", "k_cfar")), key=lambda k: kern[k]["ms_per_step"])
+    kern, dom, elapsed_prof = {}, None, None
+    if args.full:
+        # profiled repeat: per-kernel durations from HIP events on the launch stream
+        core.reset_kernel_times()
+        core.set_profiling(True)
+        elapsed_prof = timed(steps)
+        kt = core.kernel_times()
+        core.set_profiling(False)
+        kern = kernel_rooflines(wl, name, F, steps, kt, spectrum, n_cu, pmc)
+        dom = max((k for k in kern if k in ("k_range", "k_doppler", "k_cfar")), key=lambda k: kern[k]["ms_per_step"])
     value = world * F * steps / elapsed
     b_in = 8 if wl["dtype"] == "f32" else 4
     e2e_bytes = F * (ns * nc * nrx * b_in + ns * nc * 4) + 16 * n_det_step
@@ -345,14 +411,16 @@ def run_workload(name, args, world, rank, dev, primary, pmc, n_cu):
         "status_words": [int(x) for x in st],
         "e2e_GBps_algorithmic": round(e2e_bytes * steps * world / elapsed / 1e9, 1),
         "e2e_frac_of_peak": round(e2e_bytes * steps / elapsed / 1e9 / HBM_PEAK_GBPS, 4),
-        "roofline": {k: v for k, v in kern[dom].items() if k not in ("launches_per_step",)},
-        "kernels": kern,
-        "profiled_step_ms": round(elapsed_prof / steps * 1e3, 4),
+        "roofline": None,
     }
+    if args.full:
+        rec["roofline"] = {k: v for k, v in kern[dom].items() if k not in ("launches_per_step",)}
+        rec["kernels"] = kern
+        rec["profiled_step_ms"] = round(elapsed_prof / steps * 1e3, 4)
     from fmcw._lib import RANGE_KERNELS
     rec["range_kernel"] = RANGE_KERNELS[rec["range_kernel"]]
 
-    if primary and not args.no_h2d and world == 1:
+    if primary and args.full and not args.no_h2d and world == 1:
         # H2D-inclusive rate: the cube streamed from pinned host memory inside each step (copy of
         # batch i+1 on a copy stream overlapping the compute of batch i), PCIe-bound by design
         Fh = min(F, 256)
@@ -474,18 +542,18 @@ def main():
 
     rec = run_workload(args.workload, args, world, rank, dev, True, pmc, n_cu)
     subs = {}
-    if not args.no_sub and args.workload == "c2":
+    if args.full and not args.no_sub and args.workload == "c2":
         for w in ("c3", "c5"):
             subs[SUB[w]] = run_workload(w, args, world, rank, dev, False, pmc, n_cu)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, WORKLOADS[args.workload])
 
     out = {
         "metric": rec["metric"], "value": rec["value"], "unit": "frames/s", "n_gpus": world,
         "steps": rec["steps"], "warmup": rec["warmup"], "warmup_steps_run": rec["warmup_steps_run"],
         "prewarm_s": rec["prewarm_s"], "ms_per_step": rec["ms_per_step"],
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": rec["dtype"],
+        "higher_is_better": True, "full": args.full, "scaling": "weak", "vs_baseline": None, "dtype": rec["dtype"],
         "data": "synthetic (tb_radar_core-style point targets + uniform noise, int16-quantised)",
         "config": rec["config"],
         "roofline": rec["roofline"],

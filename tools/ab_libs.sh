@@ -8,7 +8,7 @@ mkdir -p $O
 for r in $(seq 1 ${ROUNDS:-2}); do
   for v in ${VARIANTS:?}; do
     FMCW_LIB=$PWD/fpga-fmcw-radar-processor_amd/lib/var_$v.so timeout -k 10 300 \
-      python bench.py --no-cpu-baseline --no-h2d > $O/${v}_$r.log 2>&1 || exit $?
+      python bench.py --full --no-cpu-baseline --no-h2d > $O/${v}_$r.log 2>&1 || exit $?
   done
 done
 for f in $O/*.log; do

@@ -9,13 +9,13 @@ export TMPDIR=/tmp
 L=$PWD/fpga-fmcw-radar-processor_amd/lib
 for r in $(seq 1 ${ROUNDS:-3}); do
   for v in ${VARIANTS:-before altdir}; do
-    FMCW_LIB=$L/var_$v.so timeout -k 10 300 python bench.py --workload ${WL:-c3} --no-cpu-baseline --no-h2d --no-sub \
+    FMCW_LIB=$L/var_$v.so timeout -k 10 300 python bench.py --full --workload ${WL:-c3} --no-cpu-baseline --no-h2d --no-sub \
       > $O/${v}_$r.log 2>&1 || exit $?
   done
 done
 for v in ${VARIANTS:-before altdir}; do
   FMCW_LIB=$L/var_$v.so timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE -d $O/fetch_$v -o run --output-format csv -- \
-    python3 bench.py --workload ${WL:-c3} --steps 2 --warmup 1 --prewarm-s 0 --no-cpu-baseline --no-h2d --no-sub > $O/fetch_$v.log 2>&1 || exit $?
+    python3 bench.py --full --workload ${WL:-c3} --steps 2 --warmup 1 --prewarm-s 0 --no-cpu-baseline --no-h2d --no-sub > $O/fetch_$v.log 2>&1 || exit $?
 done
 for f in $O/*_[0-9].log; do
   python3 - "$f" <<'PY'

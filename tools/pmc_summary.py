@@ -61,7 +61,7 @@ def main():
     ap.add_argument("--write", required=True)
     ap.add_argument("--sq", default=None)
     ap.add_argument("--frames", action="append", default=[], help="workload=frames processed in the run")
-    ap.add_argument("--command", default="python3 bench.py --steps 2 --warmup 1 --prewarm-s 0 --no-cpu-baseline --no-h2d")
+    ap.add_argument("--command", default="python3 bench.py --full --steps 2 --warmup 1 --prewarm-s 0 --no-cpu-baseline --no-h2d")
     ap.add_argument("--out", default="profiles/pmc_r05.json")
     ap.add_argument("--spectrum", action="append", default=[],
                     help="workload=f32|s48: the spectrum format the run used (algorithmic bytes; default f32)")

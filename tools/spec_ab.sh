@@ -11,7 +11,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
     lib=$PWD/fpga-fmcw-radar-processor_amd/lib/libfmcw.so
     [ "$v" != default ] && lib=$PWD/fpga-fmcw-radar-processor_amd/lib/var_$v.so
     for sp in ${SPECS:-f32 s48}; do
-      FMCW_LIB=$lib timeout -k 10 300 python bench.py --no-cpu-baseline --no-h2d --no-sub --spectrum $sp \
+      FMCW_LIB=$lib timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-h2d --no-sub --spectrum $sp \
         ${BENCH_ARGS:-} > $O/${v}_${sp}_$r.log 2>&1 || exit $?
     done
   done

@@ -5,7 +5,7 @@ set -o pipefail
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out/warmup
 mkdir -p $O
-run() { timeout -k 10 300 python bench.py "$@" --no-cpu-baseline --no-h2d > $O/$(echo "$@" | tr ' -' '_').log 2>&1; }
+run() { timeout -k 10 300 python bench.py "$@" --full --no-cpu-baseline --no-h2d > $O/$(echo "$@" | tr ' -' '_').log 2>&1; }
 run --steps 10 --warmup 3 --prewarm-s 0 &&
 run --steps 10 --warmup 100 --prewarm-s 0 &&
 run --steps 100 --warmup 3 --prewarm-s 0 &&
