@@ -34,6 +34,7 @@ PARAM_CFAR2D_STEPS = 1   # fmcw_set_param keys
 # FMCW_INFO_RANGE_KERNEL 0..3 (1 = round 2's k_range2, retired in ABI 6)
 RANGE_KERNELS = ("k_range", "k_range2 (retired)", "k_range_sq", "k_range_px")
 STATUS_WORDS = 4      # FMCW_STATUS_WORDS: n_dets_dev = found, lost, window / word saturations
+PLOT_STATUS_WORDS = 2  # FMCW_PLOT_STATUS_WORDS: n_plots_dev = plots found, records not examined
 
 STATUS_NAMES = {0: "FMCW_OK", -1: "FMCW_EINVAL", -2: "FMCW_ENOMEM", -3: "FMCW_EHIP",
                 -4: "FMCW_EDETCAP", -5: "FMCW_ENODEV"}
@@ -60,6 +61,17 @@ class FmcwConfig(C.Structure):
 class FmcwDet(C.Structure):
     _fields_ = [("frame", C.c_uint32), ("range", C.c_uint16), ("doppler", C.c_uint16),
                 ("mag", C.c_float), ("threshold", C.c_float)]
+
+
+class FmcwPlot(C.Structure):
+    _fields_ = [("frame", C.c_uint32), ("range", C.c_uint16), ("doppler", C.c_uint16),
+                ("mag", C.c_float), ("threshold", C.c_float), ("n_cells", C.c_uint32),
+                ("sum_mag", C.c_float), ("d_range", C.c_float), ("d_doppler", C.c_float)]
+
+
+class FmcwPlotsConfig(C.Structure):
+    _fields_ = [("n_range", C.c_uint32), ("n_doppler", C.c_uint32), ("win_range", C.c_uint32),
+                ("win_doppler", C.c_uint32), ("max_dets", C.c_uint32), ("device_id", C.c_int32)]
 
 
 class FmcwTwsConfig(C.Structure):
@@ -106,6 +118,10 @@ SIGNATURES = {
     "fmcw_comm_check_decide_for_test": (_I, [C.POINTER(C.c_uint64), _I, _SZ]),
     "fmcw_gather_pack_for_test": (_I, [_VP, _SZ, _VP, _SZ, C.c_uint32, _VP, _VP]),
     "fmcw_gather_compact_for_test": (_I, [_VP, _I, _SZ, _VP, _VP, _VP]),
+    "fmcw_plots_config_default": (None, [C.POINTER(FmcwPlotsConfig)]),
+    "fmcw_plots_create": (_I, [C.POINTER(FmcwPlotsConfig), C.POINTER(_VP)]),
+    "fmcw_plots_destroy": (_I, [_VP]),
+    "fmcw_plots_enqueue": (_I, [_VP, _VP, _SZ, _VP, _VP, _SZ, _VP, _VP]),
     "fmcw_tws_config_default": (None, [C.POINTER(FmcwTwsConfig)]),
     "fmcw_tws_create": (_I, [C.POINTER(FmcwTwsConfig), C.POINTER(_VP)]),
     "fmcw_tws_destroy": (_I, [_VP]),

@@ -16,6 +16,9 @@ Outputs in --out-dir (names the visualizer searches, model/visualize_radar_targe
   --doppler-centred shifts Doppler bins by N/2 (fftshift) in both files
   ADR_tracks.txt (with --tracks): the track-while-scan log, one scan per frame
                  ("TRK id R= D= Q=" / "SCAN_END ACTIVE=n", tb_radar_core.vhd:163-180)
+  ADR_plots.txt (with --plots [--plot-window R D]): one line per plot (local-maximum detection
+                 of its R x D window, fmcw.plots): "frame r d mag n_cells r+d_range d+d_doppler";
+                 with --plots, --tracks feeds the tracker each frame's plots, not its detections
 """
 from __future__ import annotations
 
@@ -25,6 +28,7 @@ from pathlib import Path
 import numpy as np
 
 from . import formats, synth
+from .plots import PlotExtractor
 from .radar_core import RadarCore, adc_words_to_cube
 from .tracker import TwsTracker
 
@@ -63,6 +67,11 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--tracks", action="store_true", help="run the TWS tracker, write ADR_tracks.txt")
     ap.add_argument("--tracker-rtl", action="store_true", help="tracker in RTL-compat mode")
+    ap.add_argument("--plots", action="store_true",
+                    help="group the detections into plots (one per local maximum), write ADR_plots.txt; "
+                         "--tracks then tracks the plots")
+    ap.add_argument("--plot-window", type=int, nargs=2, default=[1, 1], metavar=("R", "D"),
+                    help="plot window half-widths in range and Doppler bins (0..4 each)")
     ap.add_argument("--window", default="hamming", choices=["hamming", "none", "q15_rtl"])
     ap.add_argument("--doppler-centred", action="store_true",
                     help="write Doppler bins fftshifted (zero Doppler at N/2, as the visualizer assumes)")
@@ -79,11 +88,19 @@ def main(argv=None):
     if a.map_file:
         formats.write_rd_map(a.out_dir / a.map_file, out.rd_map[0], doppler_centred=a.doppler_centred)
     print(f"{nf} frame(s) {a.n_doppler}x{a.n_range}: {n} detections -> {a.out_dir / det_name}")
+    scans = out.dets
+    if a.plots:
+        with PlotExtractor(N_RANGE=a.n_range, N_DOPPLER=a.n_doppler, win=tuple(a.plot_window),
+                           max_dets=max(len(out.dets), 1), device=a.device) as px:
+            scans = px.extract(out.dets)
+        formats.write_plots(a.out_dir / "ADR_plots.txt", scans, doppler_centred=a.doppler_centred,
+                            n_doppler=a.n_doppler)
+        print(f"{len(scans)} plots (window {a.plot_window[0]} x {a.plot_window[1]}) -> {a.out_dir / 'ADR_plots.txt'}")
     if a.tracks:
         with TwsTracker(rtl_compat=a.tracker_rtl) as trk:
             hist = []
             for f in range(nf):
-                tracks = trk.scan(out.dets[out.dets["frame"] == f])
+                tracks = trk.scan(scans[scans["frame"] == f])
                 hist.append((tracks, trk.active_tracks))
         formats.write_tracks(a.out_dir / "ADR_tracks.txt", hist)
 

@@ -42,6 +42,31 @@ def write_detections(path, dets, frame: int | None = None, doppler_centred: bool
     return len(d)
 
 
+def write_plots(path, plots, doppler_centred: bool = False, n_doppler: int | None = None) -> int:
+    """Write plots (fmcw.plots.PLOT_DTYPE) as 'frame r d mag n_cells r+d_range d+d_doppler' lines:
+    the peak cell and magnitude as integers, the centroid in bins with 3 decimals (a centroid
+    across the Doppler wrap may lie below 0 or above N - 1)."""
+    dop = np.asarray(plots["doppler"], np.int64)
+    if doppler_centred:
+        if not n_doppler:
+            raise ValueError("doppler_centred needs n_doppler")
+        dop = centre_doppler(dop, n_doppler)
+    mag = np.rint(np.asarray(plots["mag"], np.float64)).astype(np.int64)
+    cr = plots["range"].astype(np.float64) + plots["d_range"]
+    cd = dop.astype(np.float64) + plots["d_doppler"]
+    with open(path, "w") as f:
+        for i in range(len(plots)):
+            f.write(f"{int(plots['frame'][i])} {int(plots['range'][i])} {int(dop[i])} {int(mag[i])} "
+                    f"{int(plots['n_cells'][i])} {cr[i]:.3f} {cd[i]:.3f}\n")
+    return len(plots)
+
+
+def read_plots(path) -> np.ndarray:
+    """The 7-column lines of write_plots as a float64 [n, 7] array."""
+    rows = [[float(x) for x in line.split()] for line in Path(path).read_text().splitlines() if line.split()]
+    return np.array(rows, np.float64).reshape(-1, 7)
+
+
 def read_detections(path) -> np.ndarray:
     """Parse like load_detections() (visualize_radar_targets.py:109-122): 3-token lines only."""
     rows = []

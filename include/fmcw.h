@@ -77,7 +77,11 @@ extern "C" {
                                   fmcw_comm_check_decide_for_test; FMCW_SPEC_S48;
                                8: fmcw_config grew det_capacity (29 words, 116 B): the detection
                                   scratch holds every cell by default, so a call loses no detection
-                                  its det_cap has room for; fmcw_comm_info */
+                                  its det_cap has room for; fmcw_comm_info.
+                               Still 8 with the plot extractor (fmcw_plots_*, fmcw_plot,
+                               fmcw_plots_config): functions and types of its own were added, and
+                               fmcw_config (29 words), FMCW_K_COUNT (4) and every existing
+                               signature are unchanged */
 
 typedef enum {
   FMCW_OK = 0,
@@ -346,6 +350,62 @@ int fmcw_device_alloc(size_t bytes, void** ptr, int device_id);
 int fmcw_device_free(void* ptr);
 int fmcw_memcpy(void* dst, const void* src, size_t bytes, int kind /*0 H2D,1 D2H,2 D2D*/);
 int fmcw_device_count(int* n);
+
+/* ---- Plot extraction (peak grouping) between the CFAR and the tracker -------------------
+ * The reference streams every CFAR output into tws_tracker (radar_core.vhd:413-438), which keeps
+ * a scan's first MAX_DETS = 64; a point target's main lobe and sidelobes are dozens of detections,
+ * so those slots go to the nearest target's cells.  The plotter turns the detection list into one
+ * fmcw_plot per local maximum, on the device, from the list alone (no map).  It is an object of
+ * its own, not part of fmcw_handle / fmcw_config.
+ *
+ * Input: a detection list as fmcw_enqueue / fmcw_cfar write it (records strictly increasing in
+ * (frame, range, doppler), range < n_range, doppler < n_doppler) and its count word.
+ * The window of a detection P = (f, r, d) is every detection (f, r + dr, (d + dd) mod n_doppler)
+ * of the same frame with |dr| <= win_range, |dd| <= win_doppler and 0 <= r + dr < n_range:
+ * Doppler is circular, range is clamped, P is in its own window.  P is a peak iff for every other
+ * Q of its window mag(P) > mag(Q), or mag(P) == mag(Q) and P precedes Q in the list.  Every peak
+ * gives one plot, in list order of the peaks.  NaN magnitudes are outside the specification. */
+typedef struct fmcw_plot {   /* 32 bytes */
+  uint32_t frame;
+  uint16_t range;            /* the peak cell */
+  uint16_t doppler;
+  float mag;                 /* the peak's record, bit for bit */
+  float threshold;
+  uint32_t n_cells;          /* detections in the window, the peak included */
+  float sum_mag;             /* S = sum of their mag (fp32, rows in ascending dr) */
+  float d_range;             /* sum(mag * dr) / S: centroid offset from the peak cell in bins, */
+  float d_doppler;           /* sum(mag * dd) / S; |.| <= win; both 0 if S is 0 or not finite */
+} fmcw_plot;
+typedef struct fmcw_plots_config {   /* 24 bytes */
+  uint32_t n_range;          /* 1..65536 */
+  uint32_t n_doppler;        /* 2 win_doppler + 1 .. 65536 */
+  uint32_t win_range;        /* 0..4 */
+  uint32_t win_doppler;      /* 0..4 */
+  uint32_t max_dets;         /* most records one call examines, 1..2^31-1; scratch: 1 bit per record
+                                and 4 B per 1024 records */
+  int32_t device_id;         /* 0..63 */
+} fmcw_plots_config;
+typedef struct fmcw_plotter fmcw_plotter;
+/* Status words of fmcw_plots_enqueue (n_plots_dev). */
+#define FMCW_PLOT_STATUS_WORDS 2
+/* Defaults: 1024, 128, window 1 x 1, max_dets 2^20, device 0. */
+void fmcw_plots_config_default(fmcw_plots_config* cfg);
+/* Validates before any device access (FMCW_EINVAL, the message names the field), then
+ * FMCW_ENODEV / FMCW_ENOMEM as fmcw_create.  Allocates all scratch. */
+int fmcw_plots_create(const fmcw_plots_config* cfg, fmcw_plotter** out);
+int fmcw_plots_destroy(fmcw_plotter* p);   /* NULL is FMCW_OK */
+/* Device pointers only; stream-ordered, allocates nothing, never synchronises, and keeps no state
+ * between calls, so it can be captured into a hipGraph after fmcw_enqueue on the same stream and
+ * replayed.  One stream at a time per plotter (its scratch is shared by its calls).
+ * Examines n = min(n_dets_dev[0], det_cap, max_dets) records (n is read on the device) and writes
+ * FMCW_PLOT_STATUS_WORDS words:
+ *   n_plots_dev[0] plots found (may exceed plot_cap: then the first plot_cap plots are written and
+ *                  nothing is stored beyond them),
+ *   n_plots_dev[1] n_dets_dev[0] - n, the records not examined.
+ * With n = 0 it writes {0, n_dets_dev[0]} and touches no plot. */
+int fmcw_plots_enqueue(fmcw_plotter* p, const fmcw_det* dets_dev, size_t det_cap,
+                       const uint32_t* n_dets_dev, fmcw_plot* plots_dev, size_t plot_cap,
+                       uint32_t* n_plots_dev, void* stream);
 
 /* ---- Track-while-scan tracker (host side) ----------------------------------------------
  * Replaces rtl/src/tws_tracker.vhd (radar_core.vhd:424-438): MAX_TRACKS alpha-beta tracks in
