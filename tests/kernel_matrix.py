@@ -14,6 +14,11 @@ Every rule cites the source it restates (paths relative to fpga-fmcw-radar-proce
 What the mirror leaves out, because it selects no other code: FMCW_WIN_NONE (the Hamming kernels
 with a table of ones, fmcw_api.hip window_table), FMCW_COMPAT_MTI (a runtime flag of the MTI
 kernels, tests/test_gpu_r02.py::test_compat_mti), range_shift, chunking and the detection scratch.
+
+The 2-D CFAR (K3a / K3b / K3c, cfar2d.hpp) is mirrored down to the branches its window geometry,
+parameters, shape and strip length select (`cfar2d_select`), and runs as a stage of its own (group
+"cfar2d") on crafted maps (`cfar2d_layout`).  The strip length the cost model picks (cfar2d_steps 0)
+depends on the CU count and has no key; one case per Doppler size and window runs it.
 """
 from __future__ import annotations
 
@@ -38,8 +43,15 @@ MAP_KINDS = ("linear", "db")
 CFAR1D_SETS = ((8, 2, 12, 4.0), (8, 2, 0, 4.0), (8, 2, 7, 4.0), (8, 2, 11, 4.0), (8, 2, 11, 1.5),
                (8, 2, 7, 1.5), (8, 2, 15, 4.0), (12, 3, 18, 4.0), (20, 3, 30, 4.0), (16, 0, 31, 4.0),
                (6, 1, 9, 3.0))
-# 2-D CFAR windows (ref_range, guard_range, ref_doppler, guard_doppler): the reference, one other
-CFAR2D_SETS = ((4, 1, 4, 2), (2, 1, 3, 1))
+# 2-D CFAR windows (ref_range, guard_range, ref_doppler, guard_doppler): the reference (n_ref 128),
+# n_ref 54, n_ref 64 without guards, n_ref 112 (above 64, no power of two), hr = 0 with hd = 21
+# beyond the halo, hd = 0 (n_ref 6), 2 hd + 1 = 31 (maximal at NC = 32), 128 cells along Doppler
+# only, hr = 8 (>= TR at NC >= 512)
+CFAR2D_SETS = ((4, 1, 4, 2), (2, 1, 3, 1), (2, 0, 6, 0), (3, 0, 5, 3), (0, 0, 20, 1), (3, 1, 0, 0),
+               (1, 0, 14, 1), (0, 0, 64, 0), (7, 1, 1, 0))
+CFAR2D_RANK_PCT = (0, 75, 100)
+CFAR2D_OVERRIDE = (0, 3)
+CFAR2D_STEPS = (1, 3, 5)
 
 SP_NAME = {0: "F32", 1: "F16", 2: "S48", 4: "S48S", 5: "S48PS"}   # kernels.hpp:127
 LOAD = {"f32": "LoadF32", "f16": "LoadF16", "i16": "LoadI16"}
@@ -63,6 +75,9 @@ class Cfg:
     cfar2d: tuple = (4, 1, 4, 2)             # ref_range, guard_range, ref_doppler, guard_doppler
     compat_cfar: bool = False
     range_shift: int = 0
+    cfar2d_rank_pct: int = 75
+    cfar2d_scales: tuple = (2, 4, 6)         # scale_min, scale_nom, scale_max
+    cfar2d_override: int = 0
 
 
 # ---- validate() ---------------------------------------------------------------------------
@@ -91,13 +106,19 @@ def illegal_reason(c: Cfg):
         if c.compat_cfar and not (alpha == int(alpha) and alpha <= 16384):   # :370
             return "compat alpha"
     elif c.cfar == "os2d":
-        rr, gr, rd, gd = c.cfar2d
-        hr, hd = rr + gr, rd + gd
-        n_ref = (2 * hr + 1) * (2 * hd + 1) - (2 * gr + 1) * (2 * gd + 1)    # cfar2_args :318
+        if c.cfar2d_rank_pct > 100:                                # :374
+            return "2-D rank_pct"
+        if max(c.cfar2d) > 64:                                     # :375
+            return "2-D window extents"
+        hr, _, hd, _, n_ref, _ = cfar2d_geom(c)
         if not 1 <= n_ref <= 128:                                  # :379
             return "2-D n_ref"
         if 2 * hd + 1 > c.n_doppler:                               # :381
             return "2-D window wider than n_doppler"
+        if c.cfar2d_override > 7:                                  # :383
+            return "2-D scale override"
+        if cfar2d_smem(c) > 160 * 1024:                            # :385
+            return "2-D range extent too large for LDS"
     if c.range_shift > 13:                                         # :394
         return "range_shift"
     if c.spectrum == "s48":
@@ -192,23 +213,107 @@ def cfar1d_keys(c: Cfg, where: str) -> set:
     return keys
 
 
-def cfar2d_select(c: Cfg):
-    """inst_cfar2.hip cfar2_info (:15-46): [(key, symbol)]."""
-    nc = c.n_doppler
+def cfar2d_geom(c: Cfg):
+    """fmcw_api.hip cfar2_args (:312-328): (hr, gr, hd, gd, n_ref, rank)."""
     rr, gr, rd, gd = c.cfar2d
-    lv = (rd + gd, gd, rr + gr, gr) == (6, 2, 5, 1)                # lv_window :15
-    if lv and nc == 1024:                                          # rules_kernel :17 (static_assert :26)
+    hr, hd = rr + gr, rd + gd
+    n_ref = (2 * hr + 1) * (2 * hd + 1) - (2 * gr + 1) * (2 * gd + 1)        # :318
+    rank = min(n_ref * c.cfar2d_rank_pct // 100, n_ref - 1)                   # :320
+    return hr, gr, hd, gd, n_ref, rank
+
+
+def cfar2d_TR(nc: int) -> int:
+    """cfar2d.hpp Cfar2DGeom<NC>::TR (:106): CUT rows of a workgroup step, WPB 4 x WR = 1024 / NC."""
+    return 4096 // nc
+
+
+def cfar2d_lv(c: Cfg) -> bool:
+    """inst_cfar2.hip lv_window (:15)."""
+    hr, gr, hd, gd, _, _ = cfar2d_geom(c)
+    return (hd, gd, hr, gr) == (6, 2, 5, 1)
+
+
+def cfar2d_smem(c: Cfg) -> int:
+    """The LDS bytes of the K3a kernel cfar2_info picks (inst_cfar2.hip info_t :20-35)."""
+    nc = c.n_doppler
+    hr = cfar2d_geom(c)[0]
+    if cfar2d_lv(c):
+        if nc == 1024:      # cfar2d.hpp LvGeom::SMEM (:849-858), HR 5: NR x ROWB + (HIST + CAPB + 2 CAPT) x 4
+            return (cfar2d_TR(nc) + 2 * 5 + 1) * (2 * (nc + 16) + nc // 2) + (144 + 192 + 2 * 64) * 4
+        hr = 5
+    # cfar2d.hpp cfar2d_smem_bytes (:131-135): (TR + 2 hr) x (RB + 2 KRS) + kCfar2dList x 4
+    return (cfar2d_TR(nc) + 2 * hr) * ((nc + 2 * MH + 16) + 2 * (nc + 2 * MH)) + (2 * 256 + 16) * 4
+
+
+def cfar2d_strips(n_range: int, nc: int, steps: int):
+    """fmcw_api.hip launch_cfar (:592-595) and the strip loop of k_cfar2d (cfar2d.hpp:543-557;
+    k_cfar2d_lv :1145-1162): [(strip index within the frame, its steps)] for a strip length."""
+    tpf = -(-n_range // cfar2d_TR(nc))                # workgroup steps per frame
+    s = min(steps, tpf)
+    return [(i, min(s, tpf - i * s)) for i in range(-(-tpf // s))]
+
+
+def cfar2d_select(c: Cfg, steps: int = 0):
+    """inst_cfar2.hip cfar2_info (:15-46): [(key, symbol)], then (key, None) for every branch of
+    cfar2d.hpp the configuration, the shape and the strip length `steps` (0: the cost model's
+    choice, which depends on the CU count and is not mirrored) take, tagged with its kernel."""
+    nc = c.n_doppler
+    hr, gr, hd, gd, n_ref, rank = cfar2d_geom(c)
+    lv = cfar2d_lv(c)                                              # lv_window :15
+    rules = lv and nc == 1024                                      # rules_kernel :17 (static_assert :26)
+    if rules:
         a = f"k_cfar2d_lv<1024, 5, 1, {'true' if c.compat_cfar else 'false'}>"
     elif lv:
         a = f"k_cfar2d<{nc}, 6, 2, 5, 1>"                          # :31
     else:
         a = f"k_cfar2d<{nc}, 0, 0, 0, 0>"                          # :21
-    return [(s.replace(" ", ""), s) for s in (a, f"k_cfar2d_decide<{nc}>", f"k_cfar2d_emit<{nc}>")]
+    out = [(s.replace(" ", ""), s) for s in (a, f"k_cfar2d_decide<{nc}>", f"k_cfar2d_emit<{nc}>")]
+    ka, kb, kc = (k for k, _ in out)
+    keys = []
+    if c.compat_cfar:
+        if not rules:                # k_cfar2d_lv carries compat in its symbol (CMP)
+            keys.append(f"{ka}/compat")                            # cfar2d.hpp:517, :674, :750 (q17 cells)
+        keys.append(f"{kb}/compat")                                # :1469 (CMP: integer mean and brackets :1440)
+        keys.append(f"{kc}/compat")                                # :1535
+    if c.cfar2d_override:
+        keys.append(f"{ka}/override")                              # :340, :378 (k_cfar2d); :1224 (k_cfar2d_lv)
+        keys.append(f"{kb}/override")                              # :1437-1438: no mean, no bracket
+    elif not c.compat_cfar:                                        # fl(sum / n) :1399-1401, :1447
+        keys.append(f"{kb}/n_ref={'pow2' if n_ref & (n_ref - 1) == 0 else 'div'}")
+    if n_ref <= 64:
+        keys.append(f"{kb}/n_ref<=64")                             # okb :1396 is never true
+    if rank == 0:                                                  # need = n_ref :498, :1090; select k = 0 :1458
+        keys += [f"{ka}/rank=0", f"{kb}/rank=0"]
+    if rank == n_ref - 1:                                          # need = 1; select k = n_ref - 1
+        keys += [f"{ka}/rank=n_ref-1", f"{kb}/rank=n_ref-1"]
+    if not lv:                       # runtime geometry of k_cfar2d<NC,0,0,0,0>
+        if hd > MH:                                                # :308, :358 wrap with & (NC - 1)
+            keys.append(f"{ka}/window>halo")
+        if 2 * hd + 1 == nc - 1:                                   # the two Doppler sides meet at the wrap
+            keys.append(f"{ka}/maximal")
+        if hr == 0:                                                # nr == TR :503, every row tested :704
+            keys.append(f"{ka}/hr=0")
+        if hd == 0:                                                # nps == 0 :302, :314: the screen counts nothing
+            keys.append(f"{ka}/hd=0")
+        if hr >= cfar2d_TR(nc):                                    # the ring turn :663 moves fewer rows than a halo
+            keys.append(f"{ka}/hr>=TR")
+    if c.n_range < cfar2d_TR(nc):                                  # n_wt < WPB :559, has_tile :694
+        keys.append(f"{ka}/step=partial")
+    if steps:
+        strips = cfar2d_strips(c.n_range, nc, steps)
+        for i, n in strips:
+            if n == 1:                                             # first == last :557: no turn, no prefetch
+                keys.append(f"{ka}/strip=one-step")
+            else:                                                  # up :554 (kK3AltDir): the turn :663, prefetch :679
+                keys.append(f"{ka}/strip={'up' if i & 1 else 'down'}")
+        if strips[-1][1] < strips[0][1]:                           # t_end = min(t_beg + steps, wg_per_frame) :543
+            keys.append(f"{ka}/strip=short-last")
+    return out + [(k, None) for k in keys]
 
 
-def select(c: Cfg, api: str = "process"):
+def select(c: Cfg, api: str = "process", steps: int = 0):
     """[(key, kernel symbol or None)] for one entry point: "process" (fmcw_enqueue), "range_ct"
-    (fmcw_range_ct) or "cfar" (fmcw_cfar)."""
+    (fmcw_range_ct) or "cfar" (fmcw_cfar; `steps`: the cfar2d_steps parameter)."""
     out = []
     nc = c.n_doppler
     if api == "range_ct":
@@ -220,7 +325,7 @@ def select(c: Cfg, api: str = "process"):
             out.append((f"k_cfar1d<{nc}>", f"k_cfar1d<{nc}>"))
             out += [(k, None) for k in cfar1d_keys(c, "stage")]
         elif c.cfar == "os2d":
-            out += cfar2d_select(c)
+            out += cfar2d_select(c, steps)
         return out
     # ---- fmcw_enqueue (:922-1006)
     sel = range_select(c.n_range, c.in_dtype, c.window, c.spectrum)
@@ -271,8 +376,8 @@ def select(c: Cfg, api: str = "process"):
     return out
 
 
-def variants(c: Cfg, api: str = "process") -> set:
-    return {k for k, _ in select(c, api)}
+def variants(c: Cfg, api: str = "process", steps: int = 0) -> set:
+    return {k for k, _ in select(c, api, steps)}
 
 
 def range_family(c: Cfg, api: str = "process") -> int:
@@ -285,9 +390,32 @@ def _cfar_options():
     for p in CFAR1D_SETS:
         yield "os1d", p, CFAR2D_SETS[0], False
     yield "os1d", CFAR1D_SETS[0], CFAR2D_SETS[0], True
-    for w in CFAR2D_SETS:
+    for w in CFAR2D_SETS[:2]:        # the whole path's two windows; cfar2d_reachable() has the rest
         for compat in (False, True):
             yield "os2d", CFAR1D_SETS[0], w, compat
+
+
+def cfar2d_shape(nc: int) -> int:
+    """n_range of the multi-step 2-D CFAR shape at a Doppler size: 8 steps, at least 64 rows."""
+    return max(64, 8 * cfar2d_TR(nc))
+
+
+def cfar2d_reachable():
+    """{key: symbol or None} of fmcw_cfar's 2-D CFAR over the windows, ranks, overrides and strip
+    lengths above, at the multi-step shape and at n_range 64 (a partial step at NC = 32).  K3 sees
+    nothing of the K1 / K2 axes, so it is enumerated on its own."""
+    found = {}
+    for nc in N_DOPPLER:
+        for ns in sorted({64, cfar2d_shape(nc)}):
+            for w, pct, ovr, compat in itertools.product(CFAR2D_SETS, CFAR2D_RANK_PCT, CFAR2D_OVERRIDE,
+                                                         (False, True)):
+                c = Cfg(n_range=ns, n_doppler=nc, window="none", cfar="os2d", cfar2d=w, compat_cfar=compat,
+                        cfar2d_rank_pct=pct, cfar2d_override=ovr)
+                if illegal_reason(c):
+                    continue
+                for steps in (0,) + CFAR2D_STEPS:
+                    found.update(select(c, "cfar", steps))
+    return found
 
 
 @functools.lru_cache(maxsize=None)
@@ -310,6 +438,7 @@ def reachable_with_symbols():
             found.update(sel)
             found.update(select(c, "range_ct"))
             found.update(select(c, "cfar"))
+    found.update(cfar2d_reachable())
     return found
 
 
@@ -335,15 +464,18 @@ for _n, _sp in ((64, 2), (128, 2), (256, 2), (512, 2), (1024, 4), (2048, 5)):
 @dataclass(frozen=True)
 class Case:
     id: str
-    group: str            # "range" (fmcw_range_ct), "process" (whole path), "cfar1d" (stage + fused)
-    cfg: Cfg
+    group: str            # "range" (fmcw_range_ct), "process" (whole path), "cfar1d" (stage + fused),
+    cfg: Cfg              # "cfar2d" (stage)
     nf: int = 2
     recipe: str = "random_target"     # synth.frames recipe; "uniform": white full-scale noise
     seed: int = 1234
+    steps: int = 0                    # the cfar2d_steps parameter (0: the cost model)
 
     def keys(self) -> set:
         if self.group == "range":
             return variants(self.cfg, "range_ct")
+        if self.group == "cfar2d":
+            return variants(self.cfg, "cfar", self.steps)
         if self.group == "cfar1d":
             return variants(self.cfg, "cfar") | variants(self.cfg, "process")
         return variants(self.cfg, "process")
@@ -356,10 +488,10 @@ def _frames_for(ns):
 def _build_cases():
     cases = []
 
-    def add(group, name, nf=2, recipe="random_target", seed=1234, **kw):
+    def add(group, name, nf=2, recipe="random_target", seed=1234, steps=0, **kw):
         c = Cfg(**kw)
         assert legal(c), (name, illegal_reason(c))
-        cases.append(Case(f"{group}-{name}", group, c, nf, recipe, seed + len(cases)))
+        cases.append(Case(f"{group}-{name}", group, c, nf, recipe, seed + len(cases), steps))
 
     # -- range stage: every (N, input type), the Q15 window at every N; n_doppler 32
     for ns in N_RANGE:
@@ -455,6 +587,38 @@ def _build_cases():
             if legal(Cfg(**kw)):        # legal() trims the sets an NC does not allow
                 add("cfar1d", f"{nc}-ref{p[0]}-g{p[1]}-rank{p[2]}-a{p[3]}", recipe="map", **kw)
         add("cfar1d", f"{nc}-compat", recipe="map", n_doppler=nc, window="none", cfar="os1d", compat_cfar=True)
+
+    # -- 2-D CFAR stage on crafted maps (cfar2d_map), 3 frames: f = g % nf mixes the frames over the
+    # strips, and nf is no multiple of 8.  At the multi-step shape (8 steps per frame) strips of 1, 3
+    # (down, up, a short down strip), 5 (down, a short up strip) and the cost model's choice on the
+    # reference window (the level screen) and (2, 1, 3, 1) (the generic kernel); every other window
+    # once; compat, rank 0 (dense: nearly every tested cell detects) and n_ref - 1, the scale
+    # override and two more scale sets on both kernels
+    def add2d(name, nc, ns, w, steps, **kw):
+        add("cfar2d", f"{nc}x{ns}-w{'.'.join(map(str, w))}-{name}", 3, "map2d", steps=steps, n_range=ns,
+            n_doppler=nc, window="none", cfar="os2d", cfar2d=w, **kw)
+
+    for nc in N_DOPPLER:
+        ns = cfar2d_shape(nc)
+        for w in CFAR2D_SETS[:2]:
+            for steps in CFAR2D_STEPS + (0,):
+                add2d(f"steps{steps}", nc, ns, w, steps)
+        for w in CFAR2D_SETS[2:]:
+            if legal(Cfg(n_range=ns, n_doppler=nc, cfar="os2d", cfar2d=w)):
+                add2d("steps3", nc, ns, w, 3)
+        for w in CFAR2D_SETS[:2]:
+            add2d("compat", nc, ns, w, 3, compat_cfar=True)
+            add2d("rank0", nc, ns, w, 3, cfar2d_rank_pct=0)
+            add2d("rank100", nc, ns, w, 3, cfar2d_rank_pct=100)
+            add2d("ovr3", nc, ns, w, 3, cfar2d_override=3)
+            add2d("scales222", nc, ns, w, 3, cfar2d_scales=(2, 2, 2))
+            add2d("scales135", nc, ns, w, 3, cfar2d_scales=(1, 3, 5))
+    # at NC = 1024 compat is a template switch of the reference window's kernel (k_cfar2d_lv CMP)
+    add2d("compat-ovr3", 1024, 64, CFAR2D_SETS[0], 3, compat_cfar=True, cfar2d_override=3)
+    add2d("compat-rank0", 1024, 64, CFAR2D_SETS[0], 3, compat_cfar=True, cfar2d_rank_pct=0)
+    add2d("compat-rank100", 1024, 64, CFAR2D_SETS[0], 3, compat_cfar=True, cfar2d_rank_pct=100)
+    for w in CFAR2D_SETS[:2]:       # n_range < TR: half a step (two wave tiles)
+        add2d("partial", 32, 64, w, 1)
     return tuple(cases)
 
 
@@ -542,12 +706,189 @@ def cfar1d_oracle(m, c: Cfg):
     return np.concatenate(dets), np.stack(masks), np.stack(thrs)
 
 
+def cfar2d_offsets(c: Cfg):
+    """The reference cells (dr, dd) of a CUT in the fixed order (fmcw_oracle.cfar2d_offsets)."""
+    hr, gr, hd, gd, _, _ = cfar2d_geom(c)
+    return [(dr, dd) for dr in range(-hr, hr + 1) for dd in range(-hd, hd + 1)
+            if not (abs(dr) <= gr and abs(dd) <= gd)]
+
+
+def cfar2d_spike_rows(case: Case):
+    """(tested, untested) range rows that carry a spike: the first and last tested rows hr and
+    ns - hr - 1, the untested rows next to them, and the two rows either side of every step
+    boundary k TR (every strip boundary is one)."""
+    c = case.cfg
+    ns, tr, hr = c.n_range, cfar2d_TR(c.n_doppler), cfar2d_geom(c)[0]
+    rows = {hr, ns - hr - 1}
+    if hr:
+        rows |= {hr - 1, ns - hr}
+    for k in range(1, -(-ns // tr)):
+        rows |= {k * tr - 1, k * tr}
+    tested = sorted(r for r in rows if hr <= r < ns - hr)
+    return tested, sorted(rows - set(tested))
+
+
+def cfar2d_scales_reachable(c: Cfg):
+    """The scales the bracket (os_cfar_2d.vhd:189-213) can choose: ranked > 1.5 mean needs a
+    reference below the ranked one (rank > 0), ranked < mean / 2 one above it (rank < n_ref - 1)."""
+    _, _, _, _, n_ref, rank = cfar2d_geom(c)
+    smin, snom, smax = c.cfar2d_scales
+    return ([smin] if rank <= n_ref - 2 else []) + [snom] + ([smax] if rank >= 1 else [])
+
+
+@functools.lru_cache(maxsize=4)
+def cfar2d_layout(case: Case):
+    """(maps [frame][range][doppler] float32, marks {name: (frame, range, doppler)}) of a 2-D CFAR
+    case, deterministic from its seed.
+
+    Rayleigh clutter (sigma 12; integer-valued for compat) with a bright patch (sigma 150) and a
+    quiet patch; a 1e30 cell, a negative cell and a -0.0 (fmcw_cfar takes both as +0).  Spikes, one per
+    row and frame so that none is a reference cell of another under the windows whose rank is
+    n_ref - 1 (hd <= 6): in tested row j of cfar2d_spike_rows at Doppler 16 j (frame 0: cells 0 and
+    16), NC - 1 - 16 j (frame 1) and 16 j + 15 (frame 2), all mod NC; in the untested rows at
+    NC / 2 + 8.  Then window-sized blocks whose centre CUT has every reference cell set by hand:
+      tie / nom_det    all references 8: mean 8, ranked 8, the nominal scale (or the override) S;
+                       centre S x 8 (cut == threshold: no detection) and S x 8 + 1
+      max_tie / _det   n_ref - rank references 64, the rest 1: ranked 64 > 1.5 mean, scale_max
+      min_tie / _det   one reference 4096, the rest 1: ranked 1 < mean / 2, scale_min
+      zero_det / zero_cut0   a block of +0 one cell wider than the window: the centre 1.0 detects
+                       (threshold 0), the +0 cell next to it does not
+      denorm_det       the same with a few 1e-40 references and the centre 1e-39 (not compat)
+    The scale blocks lie in frame 0, the zero blocks in frame 1."""
+    c = case.cfg
+    ns, nc, nf = c.n_range, c.n_doppler, case.nf
+    hr, gr, hd, gd, n_ref, rank = cfar2d_geom(c)
+    smin, snom, smax = c.cfar2d_scales
+    compat = c.compat_cfar
+    rng = np.random.default_rng(case.seed)
+    quant = np.floor if compat else (lambda x: x)
+    m = quant(rng.rayleigh(12.0, (nf, ns, nc))).astype(np.float32)
+    # the patches of test_gpu_r05_k3._clutter, scaled to the shape
+    r0, d0, pr, pd = 3 * ns // 8, nc // 5, max(ns // 12, 2 * hr + 3), max(nc // 16, 4)
+    m[:, r0:r0 + pr, d0:d0 + pd] = quant(rng.rayleigh(150.0, (nf, pr, pd)))
+    r0, d0, pr, pd = 11 * ns // 16, 5 * nc // 8, max(ns // 8, 2 * hr + 3), max(nc // 10, 4)
+    m[:, r0:r0 + pr, d0:d0 + pd] = 1.0 if compat else 0.02
+    r_odd = min(max(ns // 4 + 2, hr), ns - hr - 1)
+    if not compat:
+        m[2, r_odd, (nc // 2 + 8) % nc] = 1e30            # far above every key window (frame 2: no blocks)
+    m[2, r_odd, 8] = -5.0
+    m[2, r_odd, 10] = -0.0
+    marks = {}
+    tested, untested = cfar2d_spike_rows(case)
+    spike = (lambda r, d: 50000.0 + (16 * r + d) % 8192) if compat else (lambda r, d: 1.0e6 + 16 * r + d)
+    for j, r in enumerate(tested):
+        for f, d in enumerate((16 * j % nc, (nc - 1 - 16 * j) % nc, (16 * j + 15) % nc)):
+            m[f, r, d] = spike(r, d)
+    for r in untested:
+        m[:, r, (nc // 2 + 8) % nc] = spike(r, nc // 2 + 8)
+
+    # ---- the blocks: centres on a grid of (2 hr + 3) x (2 hd + 3) cells below the first tested row
+    band, wd = 2 * hr + 3, 2 * hd + 3
+    per = max(1, nc // wd)
+
+    def centres(n):
+        nb = -(-n // per)
+        first, last = 3 * hr + 3, ns - hr - 2
+        if len(tested) > 1 and tested[1] + hr + 2 + (nb - 1) * band <= last:
+            first = max(first, tested[1] + hr + 2)    # below the second tested spike row too (Doppler 16)
+        stride = max(band, (last - first) // nb) if nb > 1 else band
+        assert first + (nb - 1) * stride <= last, (case.id, "no room for the blocks")
+        return [(first + (i // per) * stride, (hd + 1 + (i % per) * wd) % nc) for i in range(n)]
+
+    offs = cfar2d_offsets(c)
+
+    def block(f, name, rd, refs, centre):
+        r, d = rd
+        for (dr, dd), v in zip(offs, refs):
+            m[f, r + dr, (d + dd) % nc] = v
+        m[f, r, d] = centre
+        marks[name] = (f, r, d)
+
+    s_eff = c.cfar2d_override or snom
+    todo = [("tie", [8.0] * n_ref, s_eff * 8.0), ("nom_det", [8.0] * n_ref, s_eff * 8.0 + 1)]
+    if not c.cfar2d_override:
+        if rank >= 1:                                  # cfar2d_scales_reachable
+            refs = [64.0] * (n_ref - rank) + [1.0] * rank
+            assert 64.0 > 1.5 * sum(refs) / n_ref + 1
+            todo += [("max_tie", refs, smax * 64.0), ("max_det", refs, smax * 64.0 + 1)]
+        if rank <= n_ref - 2:
+            refs = [4096.0] + [1.0] * (n_ref - 1)
+            todo += [("min_tie", refs, smin * 1.0), ("min_det", refs, smin * 1.0 + 1)]
+    for (name, refs, centre), rd in zip(todo, centres(len(todo))):
+        block(0, name, rd, refs, centre)
+    zeros = ["zero_det"] + ([] if compat else ["denorm_det"])
+    for name, (r, d) in zip(zeros, centres(len(zeros))):
+        for dd in range(-hd - 1, hd + 2):
+            m[1, r - hr - 1:r + hr + 2, (d + dd) % nc] = 0.0
+        if name == "zero_det":
+            m[1, r, d] = 1.0
+            marks[name] = (1, r, d)
+            marks["zero_cut0"] = (1, r, (d + 1) % nc) if hd else (1, r + 1, d)
+        else:
+            n_d = min(3, n_ref - rank - 1)            # the ranked reference stays +0
+            block(1, name, (r, d), [1e-40] * n_d + [0.0] * (n_ref - n_d), 1e-39)
+    m.setflags(write=False)
+    return m, marks
+
+
+def cfar2d_source_constants():
+    """(kCoopRound, the detection slot's floor and divisor with det_capacity set) read from the
+    sources: cfar2d.hpp `kCoopRound`, fmcw_create's `slot_cap` (max(floor, cells per tile / divisor))."""
+    import re
+    from pathlib import Path
+    src = Path(__file__).resolve().parent.parent / "fpga-fmcw-radar-processor_amd" / "csrc"
+    coop = re.search(r"constexpr int kCoopRound = (\d+);", (src / "cfar2d.hpp").read_text())
+    slot = re.search(r"h->slot_cap = \(uint32_t\)\(c\.det_capacity \? std::max<size_t>\((\d+), cells_tile / (\d+)\) : cells_tile\);",
+                     (src / "fmcw_api.hip").read_text())
+    assert coop and slot, "kCoopRound / slot_cap are no longer where the matrix reads them"
+    return int(coop.group(1)), int(slot.group(1)), int(slot.group(2))
+
+
+def cfar2d_dense(c: Cfg) -> bool:
+    """rank 0: the threshold is scale x the smallest reference, nearly every tested cell detects.
+    These cases run with det_capacity set (test_gpu_matrix), where a wave tile's slot holds 1/32 of
+    its cells and denser tiles move to the sink's overflow region (kernels.hpp det_reserve_wave);
+    with det_capacity 0, as every other case runs, a slot holds the whole tile."""
+    return c.cfar == "os2d" and cfar2d_geom(c)[5] == 0
+
+
+def cfar2d_map(case: Case):
+    """The [frame][range][doppler] float32 maps of a 2-D CFAR case (cfar2d_layout)."""
+    return cfar2d_layout(case)[0]
+
+
+def cfar2d_clamped(m):
+    """fmcw_cfar takes negative cells and -0.0 as +0 (kernels.hpp nonneg); the references see that map."""
+    return np.where(m > 0, m, np.float32(0.0)).astype(np.float32)
+
+
+def cfar2d_oracle(m, c: Cfg, frames=None):
+    """(detections O.DET_DTYPE, det masks, thresholds) of the NumPy oracle 2-D CFAR (RTL integers
+    for compat) on the clamped maps; `frames`: only these frames."""
+    import fmcw_oracle as O
+    p = oracle_cfar(c)
+    mc = cfar2d_clamped(m)
+    dets, masks, thrs = [], [], []
+    for f in (range(m.shape[0]) if frames is None else frames):
+        if c.compat_cfar:
+            det, thr = O.cfar_os2d_rtl(mc[f], p)
+            dets.append(O.detections_rtl(det, mc[f], thr, frame=f))
+        else:
+            det, thr = O.cfar_os2d(mc[f], p)
+            dets.append(O.detections(det, mc[f], thr, frame=f))
+        masks.append(det)
+        thrs.append(thr)
+    return np.concatenate(dets), np.stack(masks), np.stack(thrs)
+
+
 def oracle_cfar(c: Cfg):
     import fmcw_oracle as O
     if c.cfar == "os1d":
         return O.Cfar1D(*c.cfar1d[:3], alpha=c.cfar1d[3])
     rr, gr, rd, gd = c.cfar2d
-    return O.Cfar2D(ref_range=rr, guard_range=gr, ref_doppler=rd, guard_doppler=gd)
+    smin, snom, smax = c.cfar2d_scales
+    return O.Cfar2D(ref_range=rr, guard_range=gr, ref_doppler=rd, guard_doppler=gd, rank_pct=c.cfar2d_rank_pct,
+                    scale_min=smin, scale_nom=snom, scale_max=smax, scale_override=c.cfar2d_override)
 
 
 def oracle_dets(maps, c: Cfg):

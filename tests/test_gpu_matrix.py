@@ -6,12 +6,16 @@ significant bin (2e-3 per frame on the fp16 spectrum), detections bit-exact agai
 on the GPU's own map, and against the end-to-end fp64 oracle different only at near-threshold cells
 (1e-4 of the threshold; on the fp16 spectrum, which misses that by its format -- worst measured
 2.1e-3 -- plus the format's own per-row error bound, kernel_matrix.fp16_row_error).
+The 2-D CFAR stage runs crafted maps (kernel_matrix.cfar2d_layout) at every Doppler size, strip
+length, window geometry and parameter end, records bit-exact against the C oracle (the RTL-integer
+oracle for compat).
 tests/test_kernel_matrix.py shows on the CPU that the table covers the dispatch rules and that a
 correct fp32 implementation passes every case that the C restatement can run.
 """
 import numpy as np
 import pytest
 
+import cpu_backend as CB
 import fmcw_oracle as O
 import kernel_matrix as K
 from conftest import rel_err
@@ -23,6 +27,7 @@ pytestmark = pytest.mark.gpu
 RANGE = [c for c in K.CASES if c.group == "range"]
 PROCESS = [c for c in K.CASES if c.group == "process"]
 CFAR1D = [c for c in K.CASES if c.group == "cfar1d"]
+CFAR2D = [c for c in K.CASES if c.group == "cfar2d"]
 
 
 def make_core(c: K.Cfg, nf: int, **over):
@@ -31,7 +36,8 @@ def make_core(c: K.Cfg, nf: int, **over):
               magnitude=c.magnitude, map_kind=c.map_kind, cfar=c.cfar, cfar1d=c.cfar1d,
               CFAR_REF_R=rd, CFAR_GUARD_R=gd, CFAR_REF_D=rr, CFAR_GUARD_D=gr, max_frames=nf,
               mti_bypass=c.mti == 0, NOTCH_MODE=c.mti or 2, compat_rtl=("cfar",) if c.compat_cfar else (),
-              range_shift=c.range_shift, spectrum=c.spectrum)
+              range_shift=c.range_shift, spectrum=c.spectrum, cfar_rank_pct=c.cfar2d_rank_pct,
+              cfar_scales=c.cfar2d_scales, cfar_scale_ovr=c.cfar2d_override)
     kw.update(over)
     return RadarCore(**kw)
 
@@ -146,3 +152,28 @@ def test_cfar1d_stage_and_fused(gpu, case):
     cells = lambda d: set(zip(d["frame"].tolist(), d["range"].tolist(), d["doppler"].tolist()))  # noqa: E731
     # the spikes survive the round trip: the fused list is not empty at the edges either
     assert {(0, 0, 0), (0, c.n_range - 1, c.n_doppler - 1)} <= cells(out.dets) & cells(stage)
+
+
+@pytest.mark.parametrize("case", CFAR2D, ids=lambda c: c.id)
+def test_cfar2d_stage(gpu, case):
+    """fmcw_cfar with the 2-D CFAR on the case's crafted map, one launch of 3 frames at the case's
+    strip length: records (indices, mag, threshold) bit-exact against cpu_backend.cfar (compat:
+    fmcw_oracle.cfar_os2d_rtl), nothing dropped.  The rank-0 cases, where nearly every tested cell
+    detects, run with det_capacity set, so their tiles overflow the slots into the shared region."""
+    c = case.cfg
+    m = K.cfar2d_map(case)
+    over = dict(det_capacity=m.size) if K.cfar2d_dense(c) else {}
+    with make_core(c, case.nf, **over) as core:
+        if case.steps:
+            core.set_param("cfar2d_steps", case.steps)
+        got = run_cfar_stage(core, m, cap=m.size)          # asserts dropped == 0
+        if case.steps:
+            per_frame = -(-c.n_range // K.cfar2d_TR(c.n_doppler))
+            assert core.info("cfar2d_steps") == min(case.steps, per_frame)
+    if c.compat_cfar:
+        want, _, _ = K.cfar2d_oracle(m, c)
+    else:
+        want = CB.cfar(K.cfar2d_clamped(m), K.oracle_cfar(c), threads=16, cap=m.size)
+    print(f"{case.id}: {len(want)} detections")
+    assert len(want) > 0
+    np.testing.assert_array_equal(got, want)

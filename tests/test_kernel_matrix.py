@@ -1,7 +1,8 @@
 """CPU checks of the kernel test matrix (tests/kernel_matrix.py): the case table covers every
 kernel variant the dispatch rules can reach, the rules agree with the kernels the built library
 carries, and the cases' inputs are fair (a correct fp32 implementation passes them) and not
-vacuous (the 1-D CFAR maps have detections at every edge the kernels treat specially, and a tie)."""
+vacuous (the 1-D and 2-D CFAR maps have detections at every edge the kernels treat specially, and a
+tie), and the two CPU references of the 2-D CFAR agree on every 2-D map."""
 import dataclasses
 import re
 import subprocess
@@ -15,6 +16,7 @@ from test_abi import extract_code_objects
 
 PROCESS = [c for c in K.CASES if c.group == "process"]
 CFAR1D = [c for c in K.CASES if c.group == "cfar1d"]
+CFAR2D = [c for c in K.CASES if c.group == "cfar2d"]
 
 
 def test_case_ids_unique_and_legal():
@@ -45,8 +47,37 @@ def test_issue_variants_are_explicit_cases():
                 "k_doppler<1024,mti=0,S48S,FAST>/pf=0", "k_doppler<1024,mti=0,S48PS,FAST>/pf=0",
                 "k_doppler/xcd-remap<NC=1024,B=6,T=4>", "k_doppler<1024,F32,GEN>/db", "k_doppler<32,F16,GEN>/ambm", "k_doppler<64,S48,GEN>/ambm",
                 "k_range<512,LoadF16,false,0>/cw=0", "k_range<2048,LoadI16,false,0>/cw=0",
-                "k_range<1024,LoadI16,false,4>/cw=1"):
+                "k_range<1024,LoadI16,false,4>/cw=1",
+                # the 2-D CFAR: strips and the ring at the Doppler sizes that had one step or less
+                "k_cfar2d<32,6,2,5,1>/step=partial", "k_cfar2d<32,0,0,0,0>/step=partial",
+                "k_cfar2d<32,6,2,5,1>/strip=up", "k_cfar2d<32,0,0,0,0>/strip=down",
+                "k_cfar2d<64,6,2,5,1>/strip=short-last", "k_cfar2d<64,0,0,0,0>/strip=up",
+                "k_cfar2d<256,0,0,0,0>/strip=one-step", "k_cfar2d<512,6,2,5,1>/strip=down",
+                "k_cfar2d_lv<1024,5,1,false>/strip=up", "k_cfar2d_lv<1024,5,1,true>/strip=short-last",
+                # the generic kernel's runtime geometry
+                "k_cfar2d<64,0,0,0,0>/window>halo", "k_cfar2d<1024,0,0,0,0>/window>halo",
+                "k_cfar2d<32,0,0,0,0>/maximal", "k_cfar2d<128,0,0,0,0>/hr=0", "k_cfar2d<32,0,0,0,0>/hd=0",
+                "k_cfar2d<512,0,0,0,0>/hr>=TR", "k_cfar2d<1024,0,0,0,0>/hr>=TR",
+                # parameters
+                "k_cfar2d<128,0,0,0,0>/compat", "k_cfar2d<256,6,2,5,1>/compat", "k_cfar2d_decide<64>/compat",
+                "k_cfar2d<64,0,0,0,0>/override", "k_cfar2d_lv<1024,5,1,true>/override",
+                "k_cfar2d_decide<32>/override", "k_cfar2d_decide<32>/n_ref<=64", "k_cfar2d_decide<512>/n_ref=pow2",
+                "k_cfar2d_decide<512>/n_ref=div", "k_cfar2d<32,6,2,5,1>/rank=0", "k_cfar2d_decide<1024>/rank=0",
+                "k_cfar2d<1024,0,0,0,0>/rank=n_ref-1", "k_cfar2d_decide<128>/rank=n_ref-1"):
         assert key in covered, key
+    # every Doppler size: the two windows at strips of 1, 3, 5 and the cost model's, every legal
+    # window, compat, both rank ends, an override and both extra scale sets
+    for nc in K.N_DOPPLER:
+        mine = [c for c in CFAR2D if c.cfg.n_doppler == nc and c.cfg.n_range == K.cfar2d_shape(nc)]
+        for w in K.CFAR2D_SETS[:2]:
+            got = {(c.steps, c.cfg.compat_cfar, c.cfg.cfar2d_rank_pct, c.cfg.cfar2d_override, c.cfg.cfar2d_scales)
+                   for c in mine if c.cfg.cfar2d == w}
+            assert {(s, False, 75, 0, (2, 4, 6)) for s in (0, 1, 3, 5)} <= got
+            assert {(3, True, 75, 0, (2, 4, 6)), (3, False, 0, 0, (2, 4, 6)), (3, False, 100, 0, (2, 4, 6)),
+                    (3, False, 75, 3, (2, 4, 6)), (3, False, 75, 0, (2, 2, 2)), (3, False, 75, 0, (1, 3, 5))} <= got
+        legal = {w for w in K.CFAR2D_SETS if K.legal(K.Cfg(n_doppler=nc, cfar="os2d", cfar2d=w))}
+        assert legal == {c.cfg.cfar2d for c in mine}
+    assert all(c.nf == 3 and c.cfg.n_range * c.cfg.n_doppler <= 1 << 16 for c in CFAR2D)
     geoms = {(c.cfg.n_range, c.cfg.n_doppler) for c in PROCESS if c.cfg.spectrum == "s48"}
     assert {(64, 64), (128, 64), (256, 64), (512, 64), (128, 128), (1024, 1024), (2048, 1024)} <= geoms
     assert any(c.cfg.n_range == 1024 and c.cfg.n_doppler == 256 and c.cfg.n_rx == 2 for c in PROCESS)
@@ -130,3 +161,101 @@ def test_cfar1d_case_is_not_vacuous(case):
         refs = np.array([m[0, row, (dc + o) % c.n_doppler] for o in offs], np.float32)
         assert int((np.float32(alpha) * refs >= m[0, row, dc]).sum()) == n_high
         assert bool(mask[0, row, dc]) == (n_high < 2 * ref - rank)
+
+
+_ORACLE_DETS = {}       # case id -> the NumPy oracle's records, computed once for both tests below
+
+
+def _oracle2d(case):
+    if case.id not in _ORACLE_DETS:
+        dets, mask, thr = K.cfar2d_oracle(K.cfar2d_map(case), case.cfg)
+        _ORACLE_DETS[case.id] = dets
+        return dets, mask, thr
+    return _ORACLE_DETS[case.id], None, None
+
+
+def _cells(d):
+    return d["frame"].astype(int), d["range"].astype(int), d["doppler"].astype(int)
+
+
+@pytest.mark.parametrize("case", CFAR2D, ids=lambda c: c.id)
+def test_cfar2d_case_is_not_vacuous(case):
+    """The oracle's detections on the case's map (kernel_matrix.cfar2d_layout) touch every edge K3
+    treats specially, reach every scale the bracket can choose, and leave a tie undetected.
+
+    Doppler cells 0, 15, 16 and NC - 1; the first and last tested rows and none outside them; both
+    rows at every step boundary; with no override and three different scales, each scale the bracket
+    can reach chosen for a detection and for a tested cell that is none (frame 0, where the hand-made
+    windows lie; rank 0 cannot reach scale_max -- the smallest reference is never above the mean --
+    and rank n_ref - 1 cannot reach scale_min); the +0 and denormal cells; for rank 0 a step with more
+    than kCoopRound detections and a wave tile beyond its slot."""
+    c = case.cfg
+    ns, nc, tr = c.n_range, c.n_doppler, K.cfar2d_TR(c.n_doppler)
+    hr, _, _, _, n_ref, rank = K.cfar2d_geom(c)
+    m, marks = K.cfar2d_layout(case)
+    assert m.shape == (3, ns, nc) and m.dtype == np.float32
+    if c.compat_cfar:
+        assert np.array_equal(m, np.floor(m)) and m.max() <= 60000
+    else:
+        assert m.max() == np.float32(1e30)
+    assert (m < 0).any() and np.signbit(m[m == 0]).any()
+    _ORACLE_DETS.pop(case.id, None)
+    dets, mask, thr = _oracle2d(case)
+    f, r, d = _cells(dets)
+    assert 0 < len(dets)
+    assert (d == 0).any() and (d == nc - 1).any()
+    assert (d % 16 == 0).any() and (d % 16 == 15).any() and (d == 15).any() and (d == 16).any()
+    assert (r == hr).any() and (r == ns - hr - 1).any()
+    assert r.min() >= hr and r.max() < ns - hr
+    tested, untested = K.cfar2d_spike_rows(case)
+    for row in tested:          # the first and last tested rows, both rows at every step boundary
+        assert (r == row).any(), row
+    for k in range(1, -(-ns // tr)):
+        assert {k * tr - 1, k * tr} <= set(tested) | set(untested)
+    if case.steps:              # every strip boundary of the case is a step boundary
+        for i, _ in K.cfar2d_strips(ns, nc, case.steps)[1:]:
+            assert i * min(case.steps, -(-ns // tr)) * tr in set(tested) | set(untested)
+    for row in untested:        # spikes in rows whose range extent leaves the map: in no list
+        assert (m[:, row] >= 50000).any() and not (r == row).any()
+    # the tie and the hand-made windows
+    assert m[marks["tie"]] == thr[marks["tie"]] > 0 and not mask[marks["tie"]]
+    for name, at in marks.items():
+        assert bool(mask[at]) == name.endswith("_det"), name
+        if name.endswith("_tie"):
+            assert m[at] == thr[at], name
+    assert m[marks["zero_det"]] > 0 and thr[marks["zero_det"]] == 0
+    z = marks["zero_cut0"]
+    assert m[z] == 0 and not np.signbit(m[z]) and thr[z] == 0
+    if not c.compat_cfar:
+        assert 0 < m[marks["denorm_det"]] < np.finfo(np.float32).tiny
+    # the scale of every tested cell of frame 0: threshold / ranked, the ranked value being the
+    # oracle's threshold under a scale override of 1
+    scales = K.cfar2d_scales_reachable(c)
+    if not c.cfar2d_override and len(set(c.cfar2d_scales)) == 3:
+        _, _, ranked = K.cfar2d_oracle(m, dataclasses.replace(c, cfar2d_override=1), frames=(0,))
+        ranked, t0, det0 = ranked[0, hr:ns - hr], thr[0, hr:ns - hr], mask[0, hr:ns - hr]
+        for s in scales:
+            chosen = (ranked > 0) & (t0 == np.float32(s) * ranked)
+            assert (chosen & det0).any() and (chosen & ~det0).any(), s
+        assert ((ranked == 0) | np.any([t0 == np.float32(s) * ranked for s in scales], axis=0)).all()
+    else:
+        assert {"max_det", "min_det"}.isdisjoint(marks) or len(set(c.cfar2d_scales)) < 3
+    if K.cfar2d_dense(c):
+        # a second coop_rounds round (more than kCoopRound survivors in a step of 4096 cells: L = 1)
+        # and, with det_capacity set, a wave tile (1024 cells) beyond its slot: the overflow region
+        coop, slot_floor, slot_div = K.cfar2d_source_constants()
+        per_step = np.bincount(f * ns // tr + r // tr)
+        per_tile = np.bincount((f * ns + r) // (1024 // nc))
+        assert per_step.max() > coop
+        assert per_tile.max() > max(slot_floor, 1024 // slot_div)
+        assert len(dets) > m.size // 2
+
+
+@pytest.mark.parametrize("case", [c for c in CFAR2D if not c.cfg.compat_cfar], ids=lambda c: c.id)
+def test_cfar2d_references_agree(case):
+    """cpu_backend.cfar (the C oracle the GPU test compares against) and fmcw_oracle.cfar_os2d return
+    identical records on the case's map."""
+    m = K.cfar2d_map(case)
+    want, _, _ = _oracle2d(case)
+    got = CB.cfar(K.cfar2d_clamped(m), K.oracle_cfar(case.cfg), threads=4, cap=m.size)
+    np.testing.assert_array_equal(got, want)
