@@ -1,6 +1,6 @@
 // dispatch.hpp -- kernel selection tables of libfmcw.so.  Each table lives in its own
 // translation unit (inst_*.hip) so the template instantiations compile in parallel; the host
-// logic (fmcw_api.hip) sees only these function-pointer factories.
+// logic (plan.hip build_plan, once per handle) sees only these function-pointer factories.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

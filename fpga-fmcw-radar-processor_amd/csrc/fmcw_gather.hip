@@ -15,25 +15,14 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <mutex>
 
-#include "../../include/fmcw.h"
+#include "internal.hpp"
 
-int fmcw_internal_fail(int code, const char* msg);  // fmcw_api.hip: sets fmcw_last_error()
+using fmcw::fail;
 
 namespace {
-
-int gfail(int code, const char* fmt, ...) {
-  char b[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(b, sizeof b, fmt, ap);
-  va_end(ap);
-  return fmcw_internal_fail(code, b);
-}
 
 // rank-local: header + min(found, det_cap, wire_cap) records with the frame offset applied.
 // n_dets[0] may exceed det_cap (fmcw_enqueue writes at most det_cap records), so the records
@@ -107,10 +96,10 @@ bool g_fail_next_alloc = false;  // fmcw_comm_fail_next_alloc_for_test
 // n_ranks == 1) against this rank's wire_cap and allocation result.
 int comm_check_decide(const uint64_t (&h)[3], bool local_fail, size_t wire_cap, size_t msg) {
   if (h[2])
-    return local_fail ? gfail(FMCW_ENOMEM, "gather buffers (%zu B per rank) failed", msg)
-                      : gfail(FMCW_ENOMEM, "gather buffers failed on another rank");
+    return local_fail ? fail(FMCW_ENOMEM, "gather buffers (%zu B per rank) failed", msg)
+                      : fail(FMCW_ENOMEM, "gather buffers failed on another rank");
   if (h[0] != wire_cap || ~h[1] != wire_cap)
-    return gfail(FMCW_EINVAL, "wire_cap differs between ranks (this rank %zu, max %llu, min %llu)", wire_cap,
+    return fail(FMCW_EINVAL, "wire_cap differs between ranks (this rank %zu, max %llu, min %llu)", wire_cap,
                  (unsigned long long)h[0], (unsigned long long)~h[1]);
   return FMCW_OK;
 }
@@ -128,25 +117,25 @@ struct fmcw_comm {
 extern "C" {
 
 int fmcw_comm_unique_id(void* id_out) {
-  if (!id_out) return gfail(FMCW_EINVAL, "null id");
+  if (!id_out) return fail(FMCW_EINVAL, "null id");
   static_assert(sizeof(ncclUniqueId) == FMCW_COMM_ID_BYTES, "RCCL unique id size");
   ncclUniqueId id;
   const ncclResult_t r = ncclGetUniqueId(&id);
-  if (r != ncclSuccess) return gfail(FMCW_EHIP, "ncclGetUniqueId: %s", ncclGetErrorString(r));
+  if (r != ncclSuccess) return fail(FMCW_EHIP, "ncclGetUniqueId: %s", ncclGetErrorString(r));
   std::memcpy(id_out, &id, sizeof id);
   return FMCW_OK;
 }
 
 int fmcw_comm_create(const void* id, int n_ranks, int rank, int device_id, size_t wire_cap, fmcw_comm** out) {
-  if (!id || !out) return gfail(FMCW_EINVAL, "null argument");
+  if (!id || !out) return fail(FMCW_EINVAL, "null argument");
   *out = nullptr;
   if (n_ranks < 1 || n_ranks > 64 || rank < 0 || rank >= n_ranks)
-    return gfail(FMCW_EINVAL, "rank %d of %d (1..64 ranks)", rank, n_ranks);
-  if (wire_cap < 1 || wire_cap > (1u << 26)) return gfail(FMCW_EINVAL, "wire_cap %zu (1..2^26)", wire_cap);
-  if (device_id < 0 || device_id >= kMaxCommDevices) return gfail(FMCW_EINVAL, "device_id %d (0..63)", device_id);
+    return fail(FMCW_EINVAL, "rank %d of %d (1..64 ranks)", rank, n_ranks);
+  if (wire_cap < 1 || wire_cap > (1u << 26)) return fail(FMCW_EINVAL, "wire_cap %zu (1..2^26)", wire_cap);
+  if (device_id < 0 || device_id >= kMaxCommDevices) return fail(FMCW_EINVAL, "device_id %d (0..63)", device_id);
   if (hipSetDevice(device_id) != hipSuccess) {
     (void)hipGetLastError();
-    return gfail(FMCW_ENODEV, "device_id %d", device_id);
+    return fail(FMCW_ENODEV, "device_id %d", device_id);
   }
   ncclUniqueId uid;
   std::memcpy(&uid, id, sizeof uid);
@@ -158,7 +147,7 @@ int fmcw_comm_create(const void* id, int n_ranks, int rank, int device_id, size_
   const ncclResult_t r = ncclCommInitRank(&c->comm, n_ranks, uid, rank);
   if (r != ncclSuccess) {
     delete c;
-    return gfail(FMCW_EHIP, "ncclCommInitRank: %s", ncclGetErrorString(r));
+    return fail(FMCW_EHIP, "ncclCommInitRank: %s", ncclGetErrorString(r));
   }
   const size_t msg = (1 + wire_cap) * sizeof(fmcw_det);
   // A failed buffer allocation is not returned at once: every rank still joins the one all-reduce
@@ -186,7 +175,7 @@ int fmcw_comm_create(const void* id, int n_ranks, int rank, int device_id, size_
       ncclCommAbort(c->comm);
       c->comm = nullptr;
       fmcw_comm_destroy(c);
-      return gfail(FMCW_EHIP, "gather check word: hipGetSymbolAddress failed (communicator aborted)");
+      return fail(FMCW_EHIP, "gather check word: hipGetSymbolAddress failed (communicator aborted)");
     }
     ok = hipMemcpy(v, h, sizeof h, hipMemcpyHostToDevice) == hipSuccess;
     if (!ok) {  // the same: never leave the peers waiting in the collective
@@ -194,14 +183,14 @@ int fmcw_comm_create(const void* id, int n_ranks, int rank, int device_id, size_
       ncclCommAbort(c->comm);
       c->comm = nullptr;
       fmcw_comm_destroy(c);
-      return gfail(FMCW_EHIP, "gather check word: upload failed (communicator aborted)");
+      return fail(FMCW_EHIP, "gather check word: upload failed (communicator aborted)");
     }
     ok = (rr = ncclAllReduce(v, v, 3, ncclUint64, ncclMax, c->comm, nullptr)) == ncclSuccess &&
          hipMemcpy(h, v, sizeof h, hipMemcpyDeviceToHost) == hipSuccess;
     if (!ok) {
       (void)hipGetLastError();
       fmcw_comm_destroy(c);
-      return gfail(FMCW_EHIP, "gather check (all-reduce): %s", ncclGetErrorString(rr));
+      return fail(FMCW_EHIP, "gather check (all-reduce): %s", ncclGetErrorString(rr));
     }
   }
   const int rc = comm_check_decide(h, local_fail, wire_cap, msg);
@@ -224,12 +213,12 @@ int fmcw_comm_destroy(fmcw_comm* c) {
 }
 
 int fmcw_comm_info(const fmcw_comm* c, int* n_ranks, int* rank, int* device, size_t* wire_cap) {
-  if (!c || !c->comm) return gfail(FMCW_EINVAL, "null communicator");
+  if (!c || !c->comm) return fail(FMCW_EINVAL, "null communicator");
   int n = 0, r = 0, d = 0;
   ncclResult_t e = ncclCommCount(c->comm, &n);
   if (e == ncclSuccess) e = ncclCommUserRank(c->comm, &r);
   if (e == ncclSuccess) e = ncclCommCuDevice(c->comm, &d);
-  if (e != ncclSuccess) return gfail(FMCW_EHIP, "RCCL communicator query: %s", ncclGetErrorString(e));
+  if (e != ncclSuccess) return fail(FMCW_EHIP, "RCCL communicator query: %s", ncclGetErrorString(e));
   if (n_ranks) *n_ranks = n;
   if (rank) *rank = r;
   if (device) *device = d;
@@ -239,10 +228,10 @@ int fmcw_comm_info(const fmcw_comm* c, int* n_ranks, int* rank, int* device, siz
 
 int fmcw_gather_dets(fmcw_comm* c, const fmcw_det* dets_dev, size_t det_cap, const uint32_t* n_dets_dev,
                      uint32_t frame_offset, fmcw_det* out_dev, uint32_t* out_n_dev, int root, void* stream) {
-  if (!c || !dets_dev || !n_dets_dev) return gfail(FMCW_EINVAL, "null argument");
-  if (root < 0 || root >= c->n_ranks) return gfail(FMCW_EINVAL, "root %d of %d ranks", root, c->n_ranks);
-  if (c->rank == root && (!out_dev || !out_n_dev)) return gfail(FMCW_EINVAL, "root needs out_dev and out_n_dev");
-  if (hipSetDevice(c->device_id) != hipSuccess) return gfail(FMCW_EHIP, "hipSetDevice");
+  if (!c || !dets_dev || !n_dets_dev) return fail(FMCW_EINVAL, "null argument");
+  if (root < 0 || root >= c->n_ranks) return fail(FMCW_EINVAL, "root %d of %d ranks", root, c->n_ranks);
+  if (c->rank == root && (!out_dev || !out_n_dev)) return fail(FMCW_EINVAL, "root needs out_dev and out_n_dev");
+  if (hipSetDevice(c->device_id) != hipSuccess) return fail(FMCW_EHIP, "hipSetDevice");
   const size_t wire_cap = c->wire_cap;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const size_t msg = (1 + wire_cap) * sizeof(fmcw_det);
@@ -250,11 +239,11 @@ int fmcw_gather_dets(fmcw_comm* c, const fmcw_det* dets_dev, size_t det_cap, con
   hipLaunchKernelGGL(k_gather_pack, dim3(pack_blocks), dim3(256), 0, s, dets_dev,
                      (uint32_t)std::min<size_t>(det_cap, 0xffffffffu), n_dets_dev, (uint32_t)wire_cap, frame_offset,
                      c->wire);
-  if (hipGetLastError() != hipSuccess) return gfail(FMCW_EHIP, "k_gather_pack launch");
+  if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_gather_pack launch");
   if (c->rank == root) {
     if (hipMemcpyAsync(reinterpret_cast<char*>(c->recv) + (size_t)root * msg, c->wire, msg, hipMemcpyDeviceToDevice,
                        s) != hipSuccess)
-      return gfail(FMCW_EHIP, "root self copy");
+      return fail(FMCW_EHIP, "root self copy");
   }
   if (c->n_ranks > 1) {
     ncclResult_t r = ncclGroupStart();
@@ -266,13 +255,13 @@ int fmcw_gather_dets(fmcw_comm* c, const fmcw_det* dets_dev, size_t det_cap, con
     }
     const ncclResult_t r2 = ncclGroupEnd();
     if (r != ncclSuccess || r2 != ncclSuccess)
-      return gfail(FMCW_EHIP, "RCCL send/recv: %s", ncclGetErrorString(r != ncclSuccess ? r : r2));
+      return fail(FMCW_EHIP, "RCCL send/recv: %s", ncclGetErrorString(r != ncclSuccess ? r : r2));
   }
   if (c->rank == root) {
     const int blocks = (int)std::min<size_t>(256, (wire_cap + 255) / 256);
     hipLaunchKernelGGL(k_gather_compact, dim3(blocks), dim3(256), 0, s, c->recv, c->n_ranks, (uint32_t)wire_cap,
                        out_dev, out_n_dev);
-    if (hipGetLastError() != hipSuccess) return gfail(FMCW_EHIP, "k_gather_compact launch");
+    if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_gather_compact launch");
   }
   return FMCW_OK;
 }
@@ -288,7 +277,7 @@ int fmcw_comm_fail_next_alloc_for_test(int enable) {
 }
 
 int fmcw_comm_check_decide_for_test(const uint64_t* h, int local_fail, size_t wire_cap) {
-  if (!h) return gfail(FMCW_EINVAL, "null argument");
+  if (!h) return fail(FMCW_EINVAL, "null argument");
   const uint64_t w[3] = {h[0], h[1], h[2]};
   return comm_check_decide(w, local_fail != 0, wire_cap, (1 + wire_cap) * sizeof(fmcw_det));
 }
@@ -298,23 +287,23 @@ int fmcw_comm_check_decide_for_test(const uint64_t* h, int local_fail, size_t wi
 int fmcw_gather_pack_for_test(const fmcw_det* dets_dev, size_t det_cap, const uint32_t* n_dets_dev,
                               size_t wire_cap, uint32_t frame_offset, fmcw_det* msg_dev, void* stream) {
   if (!dets_dev || !n_dets_dev || !msg_dev || wire_cap < 1 || wire_cap > (1u << 26))
-    return gfail(FMCW_EINVAL, "null argument or wire_cap out of 1..2^26");
+    return fail(FMCW_EINVAL, "null argument or wire_cap out of 1..2^26");
   const int pack_blocks = (int)std::min<size_t>(1024, (wire_cap + 255) / 256);
   hipLaunchKernelGGL(k_gather_pack, dim3(pack_blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), dets_dev,
                      (uint32_t)std::min<size_t>(det_cap, 0xffffffffu), n_dets_dev, (uint32_t)wire_cap, frame_offset,
                      msg_dev);
-  if (hipGetLastError() != hipSuccess) return gfail(FMCW_EHIP, "k_gather_pack launch");
+  if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_gather_pack launch");
   return FMCW_OK;
 }
 
 int fmcw_gather_compact_for_test(const fmcw_det* msgs_dev, int n_ranks, size_t wire_cap, fmcw_det* out_dev,
                                  uint32_t* out_n_dev, void* stream) {
   if (!msgs_dev || !out_dev || !out_n_dev || n_ranks < 1 || n_ranks > 64 || wire_cap < 1 || wire_cap > (1u << 26))
-    return gfail(FMCW_EINVAL, "null argument, n_ranks out of 1..64 or wire_cap out of 1..2^26");
+    return fail(FMCW_EINVAL, "null argument, n_ranks out of 1..64 or wire_cap out of 1..2^26");
   const int blocks = (int)std::min<size_t>(256, (wire_cap + 255) / 256);
   hipLaunchKernelGGL(k_gather_compact, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), msgs_dev,
                      n_ranks, (uint32_t)wire_cap, out_dev, out_n_dev);
-  if (hipGetLastError() != hipSuccess) return gfail(FMCW_EHIP, "k_gather_compact launch");
+  if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_gather_compact launch");
   return FMCW_OK;
 }
 

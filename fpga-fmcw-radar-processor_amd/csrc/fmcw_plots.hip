@@ -28,29 +28,18 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 
-#include "../../include/fmcw.h"
+#include "internal.hpp"
 #include "plots_window.hpp"
 
-int fmcw_internal_fail(int code, const char* msg);  // fmcw_api.hip: sets fmcw_last_error()
+using fmcw::fail;
 
 static_assert(sizeof(fmcw_plot) == 32 && sizeof(fmcw_plots_config) == 24, "fmcw.h plot layouts");
 
 namespace {
 
 using namespace fmcw_plots;
-
-int pfail(int code, const char* fmt, ...) {
-  char b[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(b, sizeof b, fmt, ap);
-  va_end(ap);
-  return fmcw_internal_fail(code, b);
-}
 
 constexpr int kThreads = 256;                // 4 waves
 constexpr int kPer = 4;                      // records per lane and tile
@@ -213,13 +202,13 @@ __global__ void __launch_bounds__(kThreads) k_plots_emit(const fmcw_det* __restr
 }
 
 int validate(const fmcw_plots_config& c) {
-  if (c.n_range < 1 || c.n_range > 65536) return pfail(FMCW_EINVAL, "n_range %u (1..65536)", c.n_range);
-  if (c.win_range > 4) return pfail(FMCW_EINVAL, "win_range %u (0..4)", c.win_range);
-  if (c.win_doppler > 4) return pfail(FMCW_EINVAL, "win_doppler %u (0..4)", c.win_doppler);
+  if (c.n_range < 1 || c.n_range > 65536) return fail(FMCW_EINVAL, "n_range %u (1..65536)", c.n_range);
+  if (c.win_range > 4) return fail(FMCW_EINVAL, "win_range %u (0..4)", c.win_range);
+  if (c.win_doppler > 4) return fail(FMCW_EINVAL, "win_doppler %u (0..4)", c.win_doppler);
   if (c.n_doppler < 2 * c.win_doppler + 1 || c.n_doppler > 65536)
-    return pfail(FMCW_EINVAL, "n_doppler %u (2 win_doppler + 1 = %u .. 65536)", c.n_doppler, 2 * c.win_doppler + 1);
-  if (c.max_dets < 1 || c.max_dets > 0x7fffffffu) return pfail(FMCW_EINVAL, "max_dets %u (1..2^31-1)", c.max_dets);
-  if (c.device_id < 0 || c.device_id > 63) return pfail(FMCW_EINVAL, "device_id %d (0..63)", c.device_id);
+    return fail(FMCW_EINVAL, "n_doppler %u (2 win_doppler + 1 = %u .. 65536)", c.n_doppler, 2 * c.win_doppler + 1);
+  if (c.max_dets < 1 || c.max_dets > 0x7fffffffu) return fail(FMCW_EINVAL, "max_dets %u (1..2^31-1)", c.max_dets);
+  if (c.device_id < 0 || c.device_id > 63) return fail(FMCW_EINVAL, "device_id %d (0..63)", c.device_id);
   return FMCW_OK;
 }
 
@@ -245,23 +234,23 @@ void fmcw_plots_config_default(fmcw_plots_config* cfg) {
 }
 
 int fmcw_plots_create(const fmcw_plots_config* cfg, fmcw_plotter** out) {
-  if (!cfg || !out) return pfail(FMCW_EINVAL, "null argument");
+  if (!cfg || !out) return fail(FMCW_EINVAL, "null argument");
   *out = nullptr;
   const int rc = validate(*cfg);
   if (rc) return rc;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
     (void)hipGetLastError();
-    return pfail(FMCW_ENODEV, "no HIP device");
+    return fail(FMCW_ENODEV, "no HIP device");
   }
-  if (cfg->device_id >= ndev) return pfail(FMCW_ENODEV, "device_id %d out of range", cfg->device_id);
+  if (cfg->device_id >= ndev) return fail(FMCW_ENODEV, "device_id %d out of range", cfg->device_id);
   hipDeviceProp_t prop;
   if (hipSetDevice(cfg->device_id) != hipSuccess || hipGetDeviceProperties(&prop, cfg->device_id) != hipSuccess) {
     (void)hipGetLastError();
-    return pfail(FMCW_ENODEV, "device_id %d", cfg->device_id);
+    return fail(FMCW_ENODEV, "device_id %d", cfg->device_id);
   }
   if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return pfail(FMCW_ENODEV, "device %d is %s; this build targets gfx950 (MI355X)", cfg->device_id, prop.gcnArchName);
+    return fail(FMCW_ENODEV, "device %d is %s; this build targets gfx950 (MI355X)", cfg->device_id, prop.gcnArchName);
   fmcw_plotter* p = new fmcw_plotter();
   p->cfg = *cfg;
   p->max_tiles = (uint32_t)(((uint64_t)cfg->max_dets + kTile - 1) / kTile);
@@ -270,7 +259,7 @@ int fmcw_plots_create(const fmcw_plots_config* cfg, fmcw_plotter** out) {
       hipMalloc(reinterpret_cast<void**>(&p->tile_cnt), cnt_bytes) != hipSuccess) {
     (void)hipGetLastError();
     fmcw_plots_destroy(p);
-    return pfail(FMCW_ENOMEM, "hipMalloc(%zu + %zu) for the plotter's masks and tile counts failed", mask_bytes,
+    return fail(FMCW_ENOMEM, "hipMalloc(%zu + %zu) for the plotter's masks and tile counts failed", mask_bytes,
                  cnt_bytes);
   }
   *out = p;
@@ -288,10 +277,10 @@ int fmcw_plots_destroy(fmcw_plotter* p) {
 
 int fmcw_plots_enqueue(fmcw_plotter* p, const fmcw_det* dets_dev, size_t det_cap, const uint32_t* n_dets_dev,
                        fmcw_plot* plots_dev, size_t plot_cap, uint32_t* n_plots_dev, void* stream) {
-  if (!p || !n_dets_dev || !n_plots_dev) return pfail(FMCW_EINVAL, "null argument");
-  if (det_cap && !dets_dev) return pfail(FMCW_EINVAL, "null dets_dev with det_cap %zu", det_cap);
-  if (plot_cap && !plots_dev) return pfail(FMCW_EINVAL, "null plots_dev with plot_cap %zu", plot_cap);
-  if (hipSetDevice(p->cfg.device_id) != hipSuccess) return pfail(FMCW_EHIP, "hipSetDevice");
+  if (!p || !n_dets_dev || !n_plots_dev) return fail(FMCW_EINVAL, "null argument");
+  if (det_cap && !dets_dev) return fail(FMCW_EINVAL, "null dets_dev with det_cap %zu", det_cap);
+  if (plot_cap && !plots_dev) return fail(FMCW_EINVAL, "null plots_dev with plot_cap %zu", plot_cap);
+  if (hipSetDevice(p->cfg.device_id) != hipSuccess) return fail(FMCW_EHIP, "hipSetDevice");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const uint32_t cap = (uint32_t)std::min<size_t>(det_cap, p->cfg.max_dets);  // n = min(n_dets_dev[0], cap)
   const uint32_t pcap = (uint32_t)std::min<size_t>(plot_cap, 0x7fffffffu);     // n < 2^31 plots at most
@@ -300,14 +289,14 @@ int fmcw_plots_enqueue(fmcw_plotter* p, const fmcw_det* dets_dev, size_t det_cap
   const dim3 grid(std::min(tiles, kMaxGrid));
   if (tiles) {
     hipLaunchKernelGGL(k_plots_find, grid, dim3(kThreads), 0, s, dets_dev, cap, n_dets_dev, g, p->masks, p->tile_cnt);
-    if (hipGetLastError() != hipSuccess) return pfail(FMCW_EHIP, "k_plots_find launch");
+    if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_plots_find launch");
   }
   hipLaunchKernelGGL(k_plots_scan, dim3(1), dim3(kScanThreads), 0, s, cap, n_dets_dev, p->tile_cnt, n_plots_dev);
-  if (hipGetLastError() != hipSuccess) return pfail(FMCW_EHIP, "k_plots_scan launch");
+  if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_plots_scan launch");
   if (tiles && pcap) {
     hipLaunchKernelGGL(k_plots_emit, grid, dim3(kThreads), 0, s, dets_dev, cap, n_dets_dev, g, p->masks, p->tile_cnt,
                        plots_dev, pcap);
-    if (hipGetLastError() != hipSuccess) return pfail(FMCW_EHIP, "k_plots_emit launch");
+    if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_plots_emit launch");
   }
   return FMCW_OK;
 }

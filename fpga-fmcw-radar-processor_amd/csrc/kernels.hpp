@@ -4,7 +4,7 @@
 //  K2 k_doppler   Doppler window + FFT + |X| / NCI + map + 1-D OS-CFAR, one wave per tile
 //                                                        (radar_core.vhd:340-374, os_cfar.vhd)
 //  K3 k_cfar2d    2-D OS-CFAR over the magnitude map       (os_cfar_2d.vhd:83-230)
-//     k_det_list (fmcw_api.hip)          deterministic detection list (radar_core.vhd:396-418)
+//     k_det_list (detlist.hip)           deterministic detection list (radar_core.vhd:396-418)
 //
 // Intermediate (corner-turned range spectrum) layout in HBM, per (frame, rx):
 //     inter[rb][cb][RB][T]  complex fp32,  rb = r / RB, cb = c / T

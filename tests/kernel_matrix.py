@@ -82,7 +82,7 @@ class Cfg:
 
 # ---- validate() ---------------------------------------------------------------------------
 def illegal_reason(c: Cfg):
-    """fmcw_api.hip validate() (:341-412), in its order; None when the configuration is legal."""
+    """plan.hip validate(), in its order; None when the configuration is legal."""
     if c.n_range not in N_RANGE:                                   # :342
         return "n_range"
     if c.n_doppler not in N_DOPPLER:                               # :344
@@ -143,8 +143,8 @@ def range_T(n: int) -> int:
 
 @functools.lru_cache(maxsize=None)
 def range_select(n: int, in_dtype: str, window: str, spectrum: str):
-    """inst_range.hip range_info (:71-84) with want = kRangePx (the release library's k1_want,
-    fmcw_api.hip:237): (family, symbol, SP) or None where range_fn returns nullptr."""
+    """inst_range.hip range_info (:71-84) with want = kRangePx (the release library's preference,
+    plan.hpp PlanPrefs::k1_want): (family, symbol, SP) or None where range_fn returns nullptr."""
     q15 = window == "q15_rtl"
     ld = LOAD[in_dtype]
     if not q15 and spectrum in ("f32", "s48"):                     # :74
@@ -165,7 +165,7 @@ def range_select(n: int, in_dtype: str, window: str, spectrum: str):
 
 # ---- K2 -----------------------------------------------------------------------------------
 def k2_fast(c: Cfg) -> bool:
-    """fmcw_api.hip k2_fast (:299-309)."""
+    """plan.hip k2_fast."""
     ref, guard, rank, _ = c.cfar1d
     cfar_ok = c.cfar != "os1d" or (ref == 8 and guard == 2 and 2 * ref - rank <= 4 and not c.compat_cfar)
     return (c.mti == 0 and c.magnitude != "ambm" and c.map_kind != "db" and c.window != "q15_rtl"
@@ -214,7 +214,7 @@ def cfar1d_keys(c: Cfg, where: str) -> set:
 
 
 def cfar2d_geom(c: Cfg):
-    """fmcw_api.hip cfar2_args (:312-328): (hr, gr, hd, gd, n_ref, rank)."""
+    """plan.hip cfar2_args: (hr, gr, hd, gd, n_ref, rank)."""
     rr, gr, rd, gd = c.cfar2d
     hr, hd = rr + gr, rd + gd
     n_ref = (2 * hr + 1) * (2 * hd + 1) - (2 * gr + 1) * (2 * gd + 1)        # :318
@@ -246,7 +246,7 @@ def cfar2d_smem(c: Cfg) -> int:
 
 
 def cfar2d_strips(n_range: int, nc: int, steps: int):
-    """fmcw_api.hip launch_cfar (:592-595) and the strip loop of k_cfar2d (cfar2d.hpp:543-557;
+    """launch.hip launch_cfar (tpf, n_strips) and the strip loop of k_cfar2d (cfar2d.hpp:543-557;
     k_cfar2d_lv :1145-1162): [(strip index within the frame, its steps)] for a strip length."""
     tpf = -(-n_range // cfar2d_TR(nc))                # workgroup steps per frame
     s = min(steps, tpf)
@@ -317,7 +317,8 @@ def select(c: Cfg, api: str = "process", steps: int = 0):
     out = []
     nc = c.n_doppler
     if api == "range_ct":
-        # fmcw_api.hip:1064: the fp32-spectrum K1 whatever spectrum_dtype, no fused Doppler weight (:1075)
+        # plan.hip build_plan k1_stage (fmcw_range_ct): the fp32-spectrum K1 whatever spectrum_dtype,
+        # launched with no fused Doppler weight
         _, sym, sp = range_select(c.n_range, c.in_dtype, c.window, "f32")
         return [(sym.replace("fmcw::", "").replace(" ", "") + "/cw=0", sym)]
     if api == "cfar":
@@ -327,7 +328,7 @@ def select(c: Cfg, api: str = "process", steps: int = 0):
         elif c.cfar == "os2d":
             out += cfar2d_select(c, steps)
         return out
-    # ---- fmcw_enqueue (:922-1006)
+    # ---- fmcw_api.hip fmcw_enqueue
     sel = range_select(c.n_range, c.in_dtype, c.window, c.spectrum)
     if sel is None:
         return []
@@ -833,13 +834,13 @@ def cfar2d_layout(case: Case):
 
 def cfar2d_source_constants():
     """(kCoopRound, the detection slot's floor and divisor with det_capacity set) read from the
-    sources: cfar2d.hpp `kCoopRound`, fmcw_create's `slot_cap` (max(floor, cells per tile / divisor))."""
+    sources: cfar2d.hpp `kCoopRound`, plan.hip build_plan's `slot_cap` (max(floor, cells per tile / divisor))."""
     import re
     from pathlib import Path
     src = Path(__file__).resolve().parent.parent / "fpga-fmcw-radar-processor_amd" / "csrc"
     coop = re.search(r"constexpr int kCoopRound = (\d+);", (src / "cfar2d.hpp").read_text())
-    slot = re.search(r"h->slot_cap = \(uint32_t\)\(c\.det_capacity \? std::max<size_t>\((\d+), cells_tile / (\d+)\) : cells_tile\);",
-                     (src / "fmcw_api.hip").read_text())
+    slot = re.search(r"p\.slot_cap = \(uint32_t\)\(c\.det_capacity \? std::max<size_t>\((\d+), cells_tile / (\d+)\) : cells_tile\);",
+                     (src / "plan.hip").read_text())
     assert coop and slot, "kCoopRound / slot_cap are no longer where the matrix reads them"
     return int(coop.group(1)), int(slot.group(1)), int(slot.group(2))
 

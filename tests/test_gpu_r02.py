@@ -479,6 +479,26 @@ def test_fp16_spectrum_ambm_and_stage_api():
         assert rel_err(spec[f], ref) <= 1e-4
 
 
+@pytest.mark.parametrize("ns,nc,dtype", [
+    (4096, 32, "f32"),   # stage K1 k_range_sq, path K1 k_range<..SP_F16>
+    (8192, 32, "f16"),   # stage K1 k_range_px, path K1 k_range<..SP_F16>
+])
+def test_stage_range_ct_on_fp16_spectrum_handle(ns, nc, dtype):
+    """fmcw_range_ct on an F16-spectrum handle where the stage API's fp32-spectrum K1 is another
+    kernel family than the path's: it is launched with the path kernel's grid and un-tiled with
+    the path kernel's tile geometry.  The cube goes through the path first, so the stage call
+    finds the shared intermediate buffer used.  1e-4 per (frame, rx), as test_range_ct_parity."""
+    nf = 2
+    cube = synth.frames(nf, ns, nc, 1, "two_targets", dtype=dtype)
+    with RadarCore(N_RANGE=ns, N_DOPPLER=nc, in_dtype=dtype, cfar="none", max_frames=nf,
+                   spectrum="f16") as core:
+        core.process(cube)
+        spec = run_range_ct(core, cube, nf)
+    ref = O.range_ct(to_complex(cube, dtype))
+    for f in range(nf):
+        assert rel_err(spec[f, 0], ref[f, 0]) <= 1e-4
+
+
 @pytest.mark.parametrize("ref_r,guard_r,ref_d,guard_d,pct,scales,steps", [
     (4, 1, 4, 2, 75, (2, 4, 6), "2"),    # reference window: packed screen, strips of 2
     (4, 1, 4, 2, 90, (3, 4, 5), "0"),    # screen with need = 13, other scales

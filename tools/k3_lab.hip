@@ -24,6 +24,7 @@
 #include <functional>
 
 #include "../fpga-fmcw-radar-processor_amd/csrc/kernels.hpp"
+#include "../fpga-fmcw-radar-processor_amd/csrc/plan.hpp"  // cfar2_steps_model
 #ifdef K3_LAB_PREV  // the previous K3 (tools/cfar2d_prev.hpp, e.g. git show HEAD~:.../cfar2d.hpp) for A/B
 namespace fmcw {
 namespace prev {
@@ -81,21 +82,6 @@ struct Var {
   std::function<void(int grid, size_t smem, int n_strips, int steps, DetSink sink, Cfar2Cands cands)> launch;
 };
 
-int steps_model(int nf, int tpf, int grid, int tr, int hr) {  // = fmcw_api.hip cfar2_steps_model
-  int best = 1;
-  double best_cost = 1e300;
-  for (int S = 1; S <= std::min(64, tpf); ++S) {
-    const long strips = (long)nf * ((tpf + S - 1) / S);
-    const long rounds = (strips + grid - 1) / std::max(1, grid);
-    const double cost = (double)rounds * (1.5 * S + (double)hr / tr);
-    if (cost < best_cost - 1e-9) {
-      best_cost = cost;
-      best = S;
-    }
-  }
-  return best;
-}
-
 static int g_steps = 0;   // strip length (argv[6]; 0 = the library's cost model)
 static int g_per_cu = 0;  // workgroups per CU at most (argv[7]; 0 = occupancy)
 
@@ -103,7 +89,7 @@ template <int NC>
 int run(int nf, int reps, int ns, int nrx) {
   const float* map = nullptr;
   Cfar2DArgs a{};
-  // the reference core's 2-D CFAR parameters (fmcw_api.hip cfar2_args with the defaults)
+  // the reference core's 2-D CFAR parameters (plan.hip cfar2_args with the defaults)
   a.gr = 1;
   a.gd = 2;
   a.hr = 5;
@@ -186,7 +172,7 @@ int run(int nf, int reps, int ns, int nrx) {
     if (g_per_cu > 0) per_cu = std::min(per_cu, g_per_cu);
     const int grid_max = std::max(1, per_cu) * n_cu;
     const int tpf = (ns / WR + 3) / 4;
-    const int steps = g_steps > 0 ? std::min(g_steps, tpf) : steps_model(nf, tpf, grid_max, WR * 4, a.hr);
+    const int steps = g_steps > 0 ? std::min(g_steps, tpf) : cfar2_steps_model(nf, tpf, grid_max, WR * 4, a.hr);
     const int n_strips = nf * ((tpf + steps - 1) / steps);
     const int grid = std::min(n_strips, grid_max);
     CK(hipMemset(sink.counter, 0, 16));
