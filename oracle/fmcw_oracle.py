@@ -43,6 +43,8 @@ float32 with a fixed, documented order so detections compare bit-exactly.
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import NamedTuple
+
 import numpy as np
 
 # ---------------------------------------------------------------------------
@@ -411,6 +413,74 @@ def spectrum_words(spec_rc: np.ndarray) -> np.ndarray:
     return np.clip(np.rint(x.real), -32768, 32767) + 1j * np.clip(np.rint(x.imag), -32768, 32767)
 
 
+class WordClips(NamedTuple):
+    """Clipped samples of the 16-bit-word datapath, one count per place a sample can clip (a sample
+    counts once when its I or Q clips).  status word 2 = range_window + doppler_window, status word
+    3 = word + canceller."""
+    word: int = 0                # the spectrum rounded to the FFT IP's int16 output word
+    canceller: int = 0           # doppler_notch's saturating output (doppler_notch.vhd:76-93)
+    doppler_window: int = 0      # u_doppler_window's sat_flag, on the canceller's output words
+    range_window: int = 0        # u_range_window's sat_flag, on the ADC words: the caller's to add
+
+    @property
+    def window_saturations(self) -> int:
+        return self.range_window + self.doppler_window
+
+    @property
+    def word_saturations(self) -> int:
+        return self.word + self.canceller
+
+
+def window_q15_clips(v: np.ndarray) -> np.ndarray:
+    """window_multiplier's sat_flag (window_multiplier.vhd:152-158) per integer sample of v [..., n],
+    windowed along the last axis: the product (v c + 2^14) >> 14 leaves int16."""
+    v = np.asarray(v, np.int64)
+    n = v.shape[-1]
+    rom = hamming_q15(n)
+    half = n // 2
+    idx = np.arange(n)
+    c = rom[np.minimum(np.where(idx < half, idx, n - 1 - idx), half - 1)]
+    y = (v * c + (1 << 14)) >> 14
+    return (y < -32768) | (y > 32767)
+
+
+def range_window_clips(cube_i16: np.ndarray) -> int:
+    """Samples of a cube [..., chirp, sample, 2] whose I or Q clips in the Q15 range window."""
+    x = np.asarray(cube_i16, np.int64)
+    return int((window_q15_clips(x[..., 0]) | window_q15_clips(x[..., 1])).sum())
+
+
+def word_clips(spec_rc: np.ndarray, mti_mode: int = 0, q15_rtl: bool = True) -> WordClips:
+    """The clips after the range FFT, of a (scaled) corner-turned spectrum [..., range, chirp] whose
+    path carries 16-bit words (FMCW_COMPAT_MTI or the Q15 windows): the spectrum rounded half to
+    even to int16 (spectrum_words), the canceller's saturating output on those words, each clip
+    counted at the chirp whose output it is, and with q15_rtl the integer Doppler window on the
+    canceller's (clipped) output.  range_window is left 0."""
+    spec = np.asarray(spec_rc)
+    r = np.rint(spec.real), np.rint(spec.imag)
+    n_word = int(((np.abs(r[0] + 0.5) > 32767.5) | (np.abs(r[1] + 0.5) > 32767.5)).sum())
+    words = [np.clip(v, -32768, 32767).astype(np.int64) for v in r]
+    n_canc = 0
+    if mti_mode:
+        out = []
+        clip = np.zeros(words[0].shape, bool)
+        for v in words:
+            v1 = np.zeros_like(v)
+            v1[..., 1:] = v[..., :-1]
+            if mti_mode == 2:
+                y = v - v1
+            else:
+                v2 = np.zeros_like(v)
+                v2[..., 2:] = v[..., :-2]
+                y = v - 2 * v1 + v2
+            clip |= (y < -32768) | (y > 32767)
+            out.append(np.clip(y, -32768, 32767))
+        n_canc = int(clip.sum())
+        words = out
+    n_win = int((window_q15_clips(words[0]) | window_q15_clips(words[1])).sum()) if q15_rtl else 0
+    return WordClips(n_word, n_canc, n_win)
+
+
 def saturation_counts(cube_i16: np.ndarray, range_shift: int, mti_mode: int = 0, q15_rtl: bool = True,
                       mti_rtl: bool = False):
     """RTL-compat status as counts (fmcw.h status words 2, 3 -- the sticky status_overflow of
@@ -419,53 +489,22 @@ def saturation_counts(cube_i16: np.ndarray, range_shift: int, mti_mode: int = 0,
       window: window_multiplier's sat_flag (:152-158) in u_range_window (ADC words) and, with
               q15_rtl, in u_doppler_window (spectrum words after the canceller);
       word:   the spectrum rounded to int16 (spectrum_words) and the canceller's saturating
-              output (doppler_notch.vhd:76-93), when the path carries 16-bit words."""
+              output (doppler_notch.vhd:76-93), when the path carries 16-bit words.
+    The part after the range FFT is word_clips."""
     x = np.asarray(cube_i16, np.int64)
     if x.ndim == 3:
         x = x[None]
-    ns, nc = x.shape[-2], x.shape[-3]
-
-    def win_clips(v, n):            # v [..., n] integers, window along the last axis
-        rom = hamming_q15(n)
-        half = n // 2
-        idx = np.arange(n)
-        c = rom[np.minimum(np.where(idx < half, idx, n - 1 - idx), half - 1)]
-        y = (v * c + (1 << 14)) >> 14
-        return (y < -32768) | (y > 32767)
-
-    wsat = 0
-    words = None
     if q15_rtl:
-        wsat += int((win_clips(x[..., 0], ns) | win_clips(x[..., 1], ns)).sum())
-        c = window_q15_cube(x)
-        spec = range_ct(c, window=False)
+        spec = range_ct(window_q15_cube(x), window=False)
     else:
         spec = range_ct(x[..., 0] + 1j * x[..., 1], window=False)
     spec = spec * 2.0 ** -range_shift
-    nsat = 0
+    n = WordClips()
     if q15_rtl or mti_rtl:
-        r = np.rint(spec.real), np.rint(spec.imag)
-        nsat += int(((np.abs(r[0] + 0.5) > 32767.5) | (np.abs(r[1] + 0.5) > 32767.5)).sum())
-        words = [np.clip(r[0], -32768, 32767).astype(np.int64), np.clip(r[1], -32768, 32767).astype(np.int64)]
-        if mti_mode:
-            out = []
-            clip = np.zeros(words[0].shape, bool)
-            for v in words:
-                v1 = np.zeros_like(v)
-                v1[..., 1:] = v[..., :-1]
-                if mti_mode == 2:
-                    y = v - v1
-                else:
-                    v2 = np.zeros_like(v)
-                    v2[..., 2:] = v[..., :-2]
-                    y = v - 2 * v1 + v2
-                clip |= (y < -32768) | (y > 32767)
-                out.append(np.clip(y, -32768, 32767))
-            nsat += int(clip.sum())
-            words = out
-        if q15_rtl:
-            wsat += int((win_clips(words[0], nc) | win_clips(words[1], nc)).sum())
-    return wsat, nsat
+        n = word_clips(spec, mti_mode, q15_rtl)
+    if q15_rtl:
+        n = n._replace(range_window=range_window_clips(x))
+    return n.window_saturations, n.word_saturations
 
 
 DET_DTYPE = np.dtype([("frame", "<u4"), ("range", "<u2"), ("doppler", "<u2"),

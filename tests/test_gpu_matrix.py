@@ -9,9 +9,17 @@ on the GPU's own map, and against the end-to-end fp64 oracle different only at n
 The 2-D CFAR stage runs crafted maps (kernel_matrix.cfar2d_layout) at every Doppler size, strip
 length, window geometry and parameter end, records bit-exact against the C oracle (the RTL-integer
 oracle for compat).
+The integer (RTL-compatible) datapath is an axis of its own (test_integer_path, cases
+"process-int-*"): the canceller on the spectrum's 16-bit words and the integer Doppler window after
+it, at every Doppler size and both cancellers, on int16 cubes that clip nowhere and on cubes that
+clip at every stage.  Maps are held to the oracle's RTL arithmetic on the GPU's own range spectrum
+(1e-4; AMBM plus its two floor steps), detections bit-exact, and status words 2 and 3 exactly to the
+oracle's clip counts, which a second call on the same handle must reproduce.
 tests/test_kernel_matrix.py shows on the CPU that the table covers the dispatch rules and that a
 correct fp32 implementation passes every case that the C restatement can run.
 """
+import dataclasses
+
 import numpy as np
 import pytest
 
@@ -25,7 +33,8 @@ from test_gpu_parity import check_map, run_cfar_stage, run_range_ct
 pytestmark = pytest.mark.gpu
 
 RANGE = [c for c in K.CASES if c.group == "range"]
-PROCESS = [c for c in K.CASES if c.group == "process"]
+INTEGER = [c for c in K.CASES if c.group == "process" and c.recipe in ("int_clean", "int_sat")]
+PROCESS = [c for c in K.CASES if c.group == "process" and c not in INTEGER]
 CFAR1D = [c for c in K.CASES if c.group == "cfar1d"]
 CFAR2D = [c for c in K.CASES if c.group == "cfar2d"]
 
@@ -35,7 +44,8 @@ def make_core(c: K.Cfg, nf: int, **over):
     kw = dict(N_RANGE=c.n_range, N_DOPPLER=c.n_doppler, N_RX=c.n_rx, in_dtype=c.in_dtype, window=c.window,
               magnitude=c.magnitude, map_kind=c.map_kind, cfar=c.cfar, cfar1d=c.cfar1d,
               CFAR_REF_R=rd, CFAR_GUARD_R=gd, CFAR_REF_D=rr, CFAR_GUARD_D=gr, max_frames=nf,
-              mti_bypass=c.mti == 0, NOTCH_MODE=c.mti or 2, compat_rtl=("cfar",) if c.compat_cfar else (),
+              mti_bypass=c.mti == 0, NOTCH_MODE=c.mti or 2,
+              compat_rtl=(("cfar",) if c.compat_cfar else ()) + (("mti",) if c.compat_mti else ()),
               range_shift=c.range_shift, spectrum=c.spectrum, cfar_rank_pct=c.cfar2d_rank_pct,
               cfar_scales=c.cfar2d_scales, cfar_scale_ovr=c.cfar2d_override)
     kw.update(over)
@@ -128,6 +138,90 @@ def test_whole_path(gpu, case):
         n, rel, frac = K.check_near_threshold(out.dets, ref, c, case)
         print(f"{case.id}: {n} decisions differ from the fp64 end to end, worst |cut-thr|/thr {rel:.3g}, "
               f"worst gap/margin {frac:.3g}")
+
+
+def _run_integer(c, case, cube, **over):
+    """One handle: (process output, fmcw_cfar on its map, the range spectrum, a second process output)."""
+    with make_core(c, case.nf, **over) as core:
+        out = core.process(cube)
+        stage = run_cfar_stage(core, out.rd_map, cap=out.rd_map.size)
+        spec = run_range_ct(core, cube, case.nf)
+        assert core.info("range_kernel") == K.range_family(c)
+        assert core.info("chunk") == (over.get("chunk_frames") or case.nf)
+        again = core.process(cube)
+    return out, stage, spec, again
+
+
+def _same_output(a, b):
+    np.testing.assert_array_equal(a.rd_map.view(np.uint32), b.rd_map.view(np.uint32))
+    np.testing.assert_array_equal(a.dets, b.dets)
+    assert (a.window_saturations, a.word_saturations) == (b.window_saturations, b.word_saturations)
+
+
+@pytest.mark.parametrize("case", INTEGER, ids=lambda c: c.id)
+def test_integer_path(gpu, case):
+    """The integer datapath as a chain: i16 cube, the canceller on the spectrum's 16-bit words
+    (FMCW_COMPAT_MTI or the Q15 window), the Hamming or the integer Doppler window after it, |X|
+    with NCI or AMBM, CFAR.
+
+    Map: per frame and per significant bin within 1e-4 of the oracle's Doppler stage in RTL
+    arithmetic on the GPU's own range spectrum (a word rounds the same on both sides), and per
+    frame within 1e-4 of the fp64 end to end.  AMBM: a bin may also be off by 2, because
+    mx + floor(mn / 4) + floor(mn / 8) has two floor terms that each step by 1 when fp32 and fp64
+    fall on different sides of an integer.  Detections, fused and stage: bit-exact against the oracle
+    CFAR on the GPU's own map.  Status words 2 / 3: exactly the oracle's clips of the GPU's own
+    spectrum plus the range window's clips of the cube -- 0 on the "int_clean" cubes, non-zero on
+    "int_sat".  A second call on the same handle returns the same map, list and counts (the
+    counters are re-armed per call).  One case runs again without FMCW_COMPAT_MTI (the Q15 window
+    alone selects the words: identical bytes), one in two chunks against an unchunked handle."""
+    c = case.cfg
+    q15 = c.window == "q15_rtl"
+    ambm = c.magnitude == "ambm"
+    cube = K.make_cube(case)
+    over = dict(chunk_frames=case.chunk_frames) if case.chunk_frames else {}
+    out, stage, spec, again = _run_integer(c, case, cube, **over)
+    assert out.rd_map.shape == (case.nf, c.n_range, c.n_doppler)
+    ref = K.int_map(c, spec)
+    worst_frame = worst_bin = 0.0
+    stepped = 0
+    for f in range(case.nf):
+        x = cube[f] if q15 else K.to_complex(cube[f], "i16")
+        o = O.process(x, None, mti_mode=c.mti, q15_rtl=q15, mti_rtl=True, range_shift=c.range_shift)
+        e2e = K.ambm_f64(o["rd"][0]) if ambm else o["mag"]
+        got = out.rd_map[f].astype(np.float64)
+        big = ref[f] >= 1e-3 * ref[f].max()
+        err = np.abs(got[big] - ref[f][big])
+        stepped += int((err > 1e-4 * ref[f][big]).sum())
+        worst_bin = max(worst_bin, float(np.max((err - (2.0 if ambm else 0.0)) / ref[f][big])))
+        worst_frame = max(worst_frame, rel_err(got, ref[f]), rel_err(got, e2e))
+    print(f"{case.id}: worst frame rel err {worst_frame:.3g}, worst per-bin {worst_bin:.3g}"
+          + (f", {stepped} bins beyond 1e-4 (within the 2 floor steps)" if ambm else ""))
+    assert worst_frame <= 1e-4
+    assert worst_bin <= 1e-4          # AMBM: |got - ref| <= 1e-4 ref + 2
+    if not ambm:
+        check_map(out.rd_map, ref)
+
+    want = K.oracle_dets(out.rd_map, c)
+    np.testing.assert_array_equal(out.dets, want)
+    np.testing.assert_array_equal(stage, want)
+    assert len(want) >= 1
+
+    n = K.int_counts(c, cube, spec)
+    print(f"{case.id}: clips {tuple(n)} (word, canceller, Doppler window, range window)")
+    assert out.window_saturations == n.window_saturations
+    assert out.word_saturations == n.word_saturations
+    if case.recipe == "int_clean":
+        assert out.window_saturations == 0 and out.word_saturations == 0 and not out.status_overflow
+    else:
+        assert n.word > 0 and n.canceller > 0 and out.status_overflow == q15
+    _same_output(again, out)
+
+    if case.id.endswith("compat-same"):
+        assert q15 and c.compat_mti
+        _same_output(_run_integer(dataclasses.replace(c, compat_mti=False), case, cube)[0], out)
+    if case.chunk_frames:
+        assert case.chunk_frames < case.nf
+        _same_output(_run_integer(c, case, cube)[0], out)
 
 
 @pytest.mark.parametrize("case", CFAR1D, ids=lambda c: c.id)

@@ -2,7 +2,8 @@
 kernel variant the dispatch rules can reach, the rules agree with the kernels the built library
 carries, and the cases' inputs are fair (a correct fp32 implementation passes them) and not
 vacuous (the 1-D and 2-D CFAR maps have detections at every edge the kernels treat specially, and a
-tie), and the two CPU references of the 2-D CFAR agree on every 2-D map."""
+tie; the integer-path cubes clip nowhere or at every stage, as their recipe says), and the two CPU
+references of the 2-D CFAR agree on every 2-D map."""
 import dataclasses
 import re
 import subprocess
@@ -11,12 +12,14 @@ import numpy as np
 import pytest
 
 import cpu_backend as CB
+import fmcw_oracle as O
 import kernel_matrix as K
 from test_abi import extract_code_objects
 
 PROCESS = [c for c in K.CASES if c.group == "process"]
 CFAR1D = [c for c in K.CASES if c.group == "cfar1d"]
 CFAR2D = [c for c in K.CASES if c.group == "cfar2d"]
+INTEGER = [c for c in PROCESS if c.recipe in ("int_clean", "int_sat")]
 
 
 def test_case_ids_unique_and_legal():
@@ -48,6 +51,11 @@ def test_issue_variants_are_explicit_cases():
                 "k_doppler/xcd-remap<NC=1024,B=6,T=4>", "k_doppler<1024,F32,GEN>/db", "k_doppler<32,F16,GEN>/ambm", "k_doppler<64,S48,GEN>/ambm",
                 "k_range<512,LoadF16,false,0>/cw=0", "k_range<2048,LoadI16,false,0>/cw=0",
                 "k_range<1024,LoadI16,false,4>/cw=1",
+                # the integer datapath: the canceller on 16-bit words, the integer window after it
+                "k_doppler<32,mti=2,F32,GEN>/words", "k_doppler<32,mti=3,F32,GEN>/words",
+                "k_doppler<1024,mti=2,F32,GEN>/words", "k_doppler<1024,mti=3,F32,GEN>/words",
+                "k_doppler<32,mti=2,F32,GEN>/words+q15d", "k_doppler<32,mti=3,F32,GEN>/words+q15d",
+                "k_doppler<1024,mti=2,F32,GEN>/words+q15d", "k_doppler<1024,mti=3,F32,GEN>/words+q15d",
                 # the 2-D CFAR: strips and the ring at the Doppler sizes that had one step or less
                 "k_cfar2d<32,6,2,5,1>/step=partial", "k_cfar2d<32,0,0,0,0>/step=partial",
                 "k_cfar2d<32,6,2,5,1>/strip=up", "k_cfar2d<32,0,0,0,0>/strip=down",
@@ -81,6 +89,16 @@ def test_issue_variants_are_explicit_cases():
     geoms = {(c.cfg.n_range, c.cfg.n_doppler) for c in PROCESS if c.cfg.spectrum == "s48"}
     assert {(64, 64), (128, 64), (256, 64), (512, 64), (128, 128), (1024, 1024), (2048, 1024)} <= geoms
     assert any(c.cfg.n_range == 1024 and c.cfg.n_doppler == 256 and c.cfg.n_rx == 2 for c in PROCESS)
+    # the integer datapath: at every Doppler size and canceller, the word canceller under the
+    # Hamming and the Q15 window on a cube that clips nowhere and on one that clips, and the chain
+    for nc in K.N_DOPPLER:
+        for m in (2, 3):
+            got = {(c.cfg.window, c.cfg.compat_mti, c.recipe, c.cfg.magnitude, c.cfg.compat_cfar) for c in INTEGER
+                   if c.cfg.n_doppler == nc and c.cfg.mti == m and c.cfg.n_range == 64}
+            assert {("hamming", True, "int_clean", "abs", False), ("hamming", True, "int_sat", "abs", False),
+                    ("q15_rtl", False, "int_clean", "abs", False), ("q15_rtl", False, "int_sat", "abs", False),
+                    ("q15_rtl", True, "int_clean", "ambm", True)} <= got
+    assert any(c.chunk_frames and c.nf > c.chunk_frames and c.recipe == "int_sat" for c in INTEGER)
 
 
 def _kernel_symbols(tmp_path):
@@ -161,6 +179,60 @@ def test_cfar1d_case_is_not_vacuous(case):
         refs = np.array([m[0, row, (dc + o) % c.n_doppler] for o in offs], np.float32)
         assert int((np.float32(alpha) * refs >= m[0, row, dc]).sum()) == n_high
         assert bool(mask[0, row, dc]) == (n_high < 2 * ref - rank)
+
+
+def _components(z):
+    return np.stack([z.real, z.imag])
+
+
+@pytest.mark.parametrize("case", INTEGER, ids=lambda c: c.id)
+def test_integer_case_is_not_vacuous(case):
+    """The fp64 oracle alone on an integer-path case.  "int_clean": nothing clips at any of the four
+    places, at the smallest such range_shift, and the largest word after the canceller is at least
+    2^13 (the word range is used).  "int_sat": the spectrum words, the canceller and, with the Q15
+    window, both windows clip; the counts differ between the frames and between the rx channels; the
+    3-pulse canceller has a sample beyond 2 x 32768, which only its gain of 4 reaches.  Every case:
+    at least one detection under its CFAR.  "int_clean": every frame's peak is at least 2^11 x
+    n_doppler, a quarter of what a full-scale word gives (8192 x 0.54 x n_doppler x the canceller's
+    gain of 2), so no frame is compared at the level of single word roundings; at 2^16 and above
+    the two floor steps of AMBM are below a third of the frame-level 1e-4.  The chain (AMBM, integer
+    CFAR): the noise floor lies inside the 17-bit CFAR word."""
+    c = case.cfg
+    q15 = c.window == "q15_rtl"
+    cube = K.make_cube(case)
+    assert cube.dtype == np.int16 and cube.shape == (case.nf, c.n_rx, c.n_doppler, c.n_range, 2)
+    assert c.in_dtype == "i16" and c.mti in (2, 3) and (c.compat_mti or q15)
+    spec = K.int_spectrum(case, cube)
+    n = K.int_counts(c, cube, spec)
+    words = O.spectrum_words(spec)
+    if case.recipe == "int_clean":
+        assert n == O.WordClips(0, 0, 0, 0)
+        assert np.abs(_components(O.mti_spectrum_rtl(spec, c.mti))).max() >= 2 ** 13
+        assert sum(K.int_counts(c, cube, 2.0 * spec)) > 0          # range_shift - 1 clips
+    else:
+        assert n.word > 0 and n.canceller > 0
+        assert (n.doppler_window > 0 and n.range_window > 0) if q15 else (n.doppler_window == n.range_window == 0)
+        per_frame = [tuple(K.int_counts(c, cube[f:f + 1], spec[f:f + 1])) for f in range(case.nf)]
+        per_rx = [tuple(K.int_counts(c, cube[:, r:r + 1], spec[:, r:r + 1])) for r in range(c.n_rx)]
+        assert len(set(per_frame)) == case.nf and len(set(per_rx)) == c.n_rx == 2
+        assert tuple(map(sum, zip(*per_frame))) == tuple(n) == tuple(map(sum, zip(*per_rx)))
+        w = _components(words)
+        if c.mti == 3:
+            assert (np.abs(w[..., 2:] - 2 * w[..., 1:-1] + w[..., :-2]) > 2 * 32768).any()
+        # consecutive words of the target alternate in sign: the 2-pulse difference leaves int16 too
+        assert (np.abs(w[..., 1:] - w[..., :-1]) > 32768).any()
+    m = K.int_map(c, spec)
+    assert len(K.oracle_dets(m.astype(np.float32), c)) >= 1
+    if case.recipe == "int_clean":
+        # every frame's target survives the canceller (kernel_matrix.INT_SEED_MOVED)
+        assert min(m[f].max() for f in range(case.nf)) >= 2 ** 11 * c.n_doppler >= 2 ** 16
+    if c.magnitude == "ambm":
+        assert c.compat_cfar and c.n_rx == 1
+        assert 8 <= np.median(m) <= 2 ** 13
+    # the map from the spectrum is the end-to-end oracle's
+    x0 = cube[0] if q15 else K.to_complex(cube[0], "i16")
+    e2e = O.process(x0, None, mti_mode=c.mti, q15_rtl=q15, mti_rtl=True, range_shift=c.range_shift)
+    np.testing.assert_array_equal(K.ambm_f64(e2e["rd"][0]) if c.magnitude == "ambm" else e2e["mag"], m[0])
 
 
 _ORACLE_DETS = {}       # case id -> the NumPy oracle's records, computed once for both tests below

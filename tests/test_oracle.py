@@ -236,3 +236,63 @@ def test_mti_spectrum_rtl():
     np.testing.assert_array_equal(y.real[0], [0, 2, 0, 32765, -32768, 32767])
     y3 = O.mti_spectrum_rtl(x, 3)
     np.testing.assert_array_equal(y3.real[0], [0, 2, -2, 32765, -32768, 32767])
+
+
+def _sat_cubes():
+    rng = np.random.default_rng(77)
+    a = rng.integers(-32768, 32768, (2, 32, 64, 2)).astype(np.int16)          # full-scale noise, 2 rx
+    b = np.zeros((1, 32, 64, 2), np.int16)                                    # chirps of alternating sign
+    b[..., 0] = (1000 * np.where(np.arange(32) % 2 == 0, 1, -1))[None, :, None]
+    b[..., 1] = rng.integers(-300, 300, (1, 32, 64))
+    return a, b
+
+
+# (cube, range_shift, mti_mode, q15_rtl, mti_rtl) -> (window, word) saturations, as saturation_counts
+# returned them before word_clips was split out of it
+_SAT_RECORDED = {
+    (0, 3, 0, True, False): (2213, 673), (0, 3, 0, False, True): (0, 634),
+    (0, 3, 2, True, False): (2580, 2114), (0, 3, 2, False, True): (0, 2001),
+    (0, 3, 3, True, False): (2987, 3526), (0, 3, 3, False, True): (0, 3452),
+    (0, 4, 2, True, False): (1746, 115), (0, 4, 3, False, True): (0, 1112),
+    (0, 5, 3, True, True): (1556, 32), (0, 6, 3, True, False): (1223, 0), (0, 6, 3, False, False): (0, 0),
+    (1, 0, 0, True, False): (48, 33), (1, 0, 0, False, True): (0, 32),
+    (1, 0, 2, True, False): (48, 126), (1, 0, 2, False, True): (0, 63),
+    (1, 0, 3, True, False): (48, 126), (1, 1, 2, True, False): (47, 63),
+    (1, 1, 3, True, False): (48, 125), (1, 1, 3, False, True): (0, 31), (1, 1, 0, False, True): (0, 0),
+}
+
+
+def test_word_clips_by_hand():
+    """word_clips on a row whose clips can be counted by hand: words 0, 2, 2, 32767, -32768, 3."""
+    x = np.array([[0.5, 1.5, 2.5, 40000.0, -40000.0, 3.0]]) + 0j
+    assert O.word_clips(x, 0, False) == O.WordClips(word=2)
+    # 2-pulse: 32765, -65535, 32771; 3-pulse: 32765, -98300 (= -32768 - 2 x 32767 + 2), 65539 + 32767
+    assert O.word_clips(x, 2, False) == O.WordClips(word=2, canceller=2)
+    assert O.word_clips(x, 3, False) == O.WordClips(word=2, canceller=2)
+    # the 6-point Q15 ROM is (2621, 13044, 29890), mirrored: the window's gain 2 c / 32768 on the
+    # canceller's output 0, 2, 0, 32765, -32768, 32767 is 1.82 at chirp 3 (clips), 0.80 and 0.16 after
+    n = O.word_clips(x, 2, True)
+    assert (n.word, n.canceller, n.doppler_window, n.range_window) == (2, 2, 1, 0)
+    assert n.window_saturations == 1 and n.word_saturations == 4
+    # the window sees the canceller's clipped output: unclipped, chirp 4 (-65535 x 0.80) would clip too
+    assert O.word_clips(x, 0, True).doppler_window == 1         # words 32767 at chirp 3 only
+
+
+def test_saturation_counts_unchanged_by_the_split():
+    """saturation_counts returns the recorded totals on two small cubes, and they are the sum of
+    word_clips' separate counts on the same spectrum plus the range window's clips on the cube."""
+    cubes = _sat_cubes()
+    seen = [0, 0, 0, 0]
+    for (k, shift, mti, q15, rtl), want in _SAT_RECORDED.items():
+        cube = cubes[k]
+        assert O.saturation_counts(cube, shift, mti, q15, rtl) == want, (k, shift, mti, q15, rtl)
+        if not (q15 or rtl):
+            continue
+        x = O.window_q15_cube(cube) if q15 else cube[..., 0].astype(np.float64) + 1j * cube[..., 1]
+        spec = O.range_ct(x, window=False) * 2.0 ** -shift
+        n = O.word_clips(spec, mti, q15)
+        assert n.range_window == 0 and (mti or n.canceller == 0) and (q15 or n.doppler_window == 0)
+        rw = O.range_window_clips(cube) if q15 else 0
+        assert (rw + n.doppler_window, n.word + n.canceller) == want
+        seen = [s + v for s, v in zip(seen, (n.word, n.canceller, n.doppler_window, rw))]
+    assert all(seen)            # every one of the four counts took part
