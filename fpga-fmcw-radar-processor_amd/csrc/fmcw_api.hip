@@ -419,14 +419,42 @@ int fmcw_set_profiling(fmcw_handle* h, int enable) {
   return FMCW_OK;
 }
 
+namespace {
+
+// FMCW_PARAM_GRID_* / FMCW_INFO_GRID_*: the fmcw_grids field of a key, or nullptr
+struct GridKey {
+  int param, info;
+  const char* name;
+  int fmcw_grids::*field;
+};
+constexpr GridKey kGridKeys[] = {
+    {FMCW_PARAM_GRID_RANGE, FMCW_INFO_GRID_RANGE, "grid_range", &fmcw_grids::range},
+    {FMCW_PARAM_GRID_DOPPLER, FMCW_INFO_GRID_DOPPLER, "grid_doppler", &fmcw_grids::doppler},
+    {FMCW_PARAM_GRID_CFAR2D, FMCW_INFO_GRID_CFAR2D, "grid_cfar2d", &fmcw_grids::cfar},
+    {FMCW_PARAM_GRID_K3B, FMCW_INFO_GRID_K3B, "grid_k3b", &fmcw_grids::k3b},
+    {FMCW_PARAM_GRID_K3C, FMCW_INFO_GRID_K3C, "grid_k3c", &fmcw_grids::k3c},
+};
+
+}  // namespace
+
+// The key and the value are checked before the handle, so the reject ranges hold without a device.
 int fmcw_set_param(fmcw_handle* h, int key, int64_t value) {
-  if (!h) return fail(FMCW_EINVAL, "null handle");
-  switch (key) {
-    case FMCW_PARAM_CFAR2D_STEPS:
-      if (value < 0 || value > (1 << 20)) return fail(FMCW_EINVAL, "cfar2d steps %lld (0 = cost model)", (long long)value);
-      h->cfar2_steps = (int)value;
-      return FMCW_OK;
+  if (key == FMCW_PARAM_CFAR2D_STEPS) {
+    if (value < 0 || value > (1 << 20)) return fail(FMCW_EINVAL, "cfar2d steps %lld (0 = cost model)", (long long)value);
+    if (!h) return fail(FMCW_EINVAL, "null handle");
+    h->cfar2_steps = (int)value;
+    return FMCW_OK;
   }
+  for (const GridKey& k : kGridKeys) {
+    if (key != k.param) continue;
+    if (value < 0 || value > (1 << 20))
+      return fail(FMCW_EINVAL, "%s %lld (0 = the created grid, 1..2^20 = a cap)", k.name, (long long)value);
+    if (!h) return fail(FMCW_EINVAL, "null handle");
+    const int created = h->grid_created.*k.field;
+    h->grid.*k.field = value ? std::min(created, (int)value) : created;
+    return FMCW_OK;
+  }
+  if (!h) return fail(FMCW_EINVAL, "null handle");
   return fail(FMCW_EINVAL, "fmcw_set_param: unknown key %d", key);
 }
 
@@ -439,6 +467,11 @@ int fmcw_get_info(fmcw_handle* h, int key, int64_t* value) {
     case FMCW_INFO_WORD_SATURATIONS: *value = h->last_status[1]; return FMCW_OK;
     case FMCW_INFO_CFAR2D_STEPS: *value = h->cfar2_steps_last; return FMCW_OK;
   }
+  for (const GridKey& k : kGridKeys)
+    if (key == k.info) {
+      *value = h->grid.*k.field;
+      return FMCW_OK;
+    }
   return fail(FMCW_EINVAL, "fmcw_get_info: unknown key %d", key);
 }
 

@@ -217,6 +217,7 @@ int validate(const fmcw_plots_config& c) {
 struct fmcw_plotter {
   fmcw_plots_config cfg;
   uint32_t max_tiles = 0;
+  uint32_t grid = kMaxGrid;      // workgroups of find / emit at most (fmcw_plots_set_grid_for_test)
   uint64_t* masks = nullptr;     // kGroups per tile: 1 bit per record
   uint32_t* tile_cnt = nullptr;  // per tile: peak count, then its exclusive scan
 };
@@ -275,6 +276,12 @@ int fmcw_plots_destroy(fmcw_plotter* p) {
   return FMCW_OK;
 }
 
+int fmcw_plots_set_grid_for_test(fmcw_plotter* p, uint32_t grid) {
+  if (!p) return fail(FMCW_EINVAL, "null plotter");
+  p->grid = grid ? std::min(kMaxGrid, grid) : kMaxGrid;
+  return FMCW_OK;
+}
+
 int fmcw_plots_enqueue(fmcw_plotter* p, const fmcw_det* dets_dev, size_t det_cap, const uint32_t* n_dets_dev,
                        fmcw_plot* plots_dev, size_t plot_cap, uint32_t* n_plots_dev, void* stream) {
   if (!p || !n_dets_dev || !n_plots_dev) return fail(FMCW_EINVAL, "null argument");
@@ -286,7 +293,7 @@ int fmcw_plots_enqueue(fmcw_plotter* p, const fmcw_det* dets_dev, size_t det_cap
   const uint32_t pcap = (uint32_t)std::min<size_t>(plot_cap, 0x7fffffffu);     // n < 2^31 plots at most
   const uint32_t tiles = (uint32_t)(((uint64_t)cap + kTile - 1) / kTile);       // <= max_tiles
   const PlotGeom g = {p->cfg.n_range, p->cfg.n_doppler, p->cfg.win_range, p->cfg.win_doppler};
-  const dim3 grid(std::min(tiles, kMaxGrid));
+  const dim3 grid(std::min(tiles, p->grid));
   if (tiles) {
     hipLaunchKernelGGL(k_plots_find, grid, dim3(kThreads), 0, s, dets_dev, cap, n_dets_dev, g, p->masks, p->tile_cnt);
     if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_plots_find launch");

@@ -6,7 +6,8 @@
 #include "plan.hpp"
 #include "profiling.hpp"
 
-// The persistent grids: workgroups the device holds at once (occupancy x CUs), fixed at fmcw_create.
+// The persistent grids: workgroups the device holds at once (occupancy x CUs), computed at
+// fmcw_create; fmcw_set_param (FMCW_PARAM_GRID_*) can cap each below its created value.
 struct fmcw_grids {
   int range = 0, doppler = 0, cfar = 0;  // K1, K2 (and the stand-alone 1-D CFAR), K3a
   int k3b = 0, k3c = 0;                  // K3b / K3c (kCfar2DecideGrid / kCfar2EmitGrid)
@@ -14,7 +15,8 @@ struct fmcw_grids {
 
 struct fmcw_handle {
   const fmcw::Plan plan;
-  const fmcw_grids grid;
+  const fmcw_grids grid_created;  // as fmcw_create computed them
+  fmcw_grids grid;                // the launches' bounds: min(created, FMCW_PARAM_GRID_* cap)
   // device buffers
   float* win_r = nullptr;  // [ns]
   float* win_d = nullptr;  // [nc]
@@ -53,7 +55,7 @@ struct fmcw_handle {
   uint32_t last_status[2] = {0, 0};     // fmcw_process: status words 2, 3 of its last call
   fmcw::Profiler prof;
 
-  fmcw_handle(const fmcw::Plan& p, const fmcw_grids& g) : plan(p), grid(g) {}
+  fmcw_handle(const fmcw::Plan& p, const fmcw_grids& g) : plan(p), grid_created(g), grid(g) {}
 };
 
 namespace fmcw {

@@ -30,7 +30,13 @@ K_RANGE, K_DOPPLER, K_CFAR2D, K_COMPACT, K_COUNT = 0, 1, 2, 3, 4
 KERNEL_NAMES = ("k_range", "k_doppler", "k_cfar", "k_compact")
 INFO_CHUNK, INFO_RANGE_KERNEL, INFO_WINDOW_SATURATIONS, INFO_WORD_SATURATIONS = 4, 6, 7, 8
 INFO_CFAR2D_STEPS = 9
+INFO_GRID_RANGE, INFO_GRID_DOPPLER, INFO_GRID_CFAR2D, INFO_GRID_K3B, INFO_GRID_K3C = 10, 11, 12, 13, 14
 PARAM_CFAR2D_STEPS = 1   # fmcw_set_param keys
+PARAM_GRID_RANGE, PARAM_GRID_DOPPLER, PARAM_GRID_CFAR2D, PARAM_GRID_K3B, PARAM_GRID_K3C = 2, 3, 4, 5, 6
+# the persistent grids: the name RadarCore.set_param / .info take -> (FMCW_PARAM_GRID_*, FMCW_INFO_GRID_*)
+GRID_KEYS = {"grid_range": (PARAM_GRID_RANGE, INFO_GRID_RANGE), "grid_doppler": (PARAM_GRID_DOPPLER, INFO_GRID_DOPPLER),
+             "grid_cfar2d": (PARAM_GRID_CFAR2D, INFO_GRID_CFAR2D), "grid_k3b": (PARAM_GRID_K3B, INFO_GRID_K3B),
+             "grid_k3c": (PARAM_GRID_K3C, INFO_GRID_K3C)}
 # FMCW_INFO_RANGE_KERNEL 0..3 (1 = round 2's k_range2, retired in ABI 6)
 RANGE_KERNELS = ("k_range", "k_range2 (retired)", "k_range_sq", "k_range_px")
 STATUS_WORDS = 4      # FMCW_STATUS_WORDS: n_dets_dev = found, lost, window / word saturations
@@ -122,6 +128,7 @@ SIGNATURES = {
     "fmcw_plots_create": (_I, [C.POINTER(FmcwPlotsConfig), C.POINTER(_VP)]),
     "fmcw_plots_destroy": (_I, [_VP]),
     "fmcw_plots_enqueue": (_I, [_VP, _VP, _SZ, _VP, _VP, _SZ, _VP, _VP]),
+    "fmcw_plots_set_grid_for_test": (_I, [_VP, C.c_uint32]),
     "fmcw_tws_config_default": (None, [C.POINTER(FmcwTwsConfig)]),
     "fmcw_tws_create": (_I, [C.POINTER(FmcwTwsConfig), C.POINTER(_VP)]),
     "fmcw_tws_destroy": (_I, [_VP]),

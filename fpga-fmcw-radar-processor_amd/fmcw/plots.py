@@ -80,6 +80,11 @@ class PlotExtractor:
             dn.free()
             ds.free()
 
+    def set_grid_for_test(self, grid: int) -> None:
+        """fmcw_plots_set_grid_for_test: at most `grid` workgroups for the two tile kernels (0: the
+        built-in bound), so that a short list drives a workgroup through several tiles."""
+        L.check(self._lib.fmcw_plots_set_grid_for_test(self._h, int(grid)))
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             self._lib.fmcw_plots_destroy(self._h)

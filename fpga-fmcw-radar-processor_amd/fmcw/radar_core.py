@@ -275,8 +275,11 @@ class RadarCore:
 
     def set_param(self, key: str, value: int) -> None:
         """fmcw_set_param (tuning; results never depend on it): "cfar2d_steps" = 2-D CFAR steps
-        per strip, 0 = the library's cost model."""
-        k = {"cfar2d_steps": L.PARAM_CFAR2D_STEPS}[key]
+        per strip, 0 = the library's cost model; "grid_range", "grid_doppler" (K2 and the stand-alone
+        1-D CFAR), "grid_cfar2d", "grid_k3b", "grid_k3c" = a cap on that persistent kernel's
+        workgroups, 0 = the grid computed at creation.  A captured graph keeps the grids it was
+        captured with."""
+        k = {"cfar2d_steps": L.PARAM_CFAR2D_STEPS, **{n: p for n, (p, _) in L.GRID_KEYS.items()}}[key]
         L.check(self._lib.fmcw_set_param(self._h, k, int(value)))
 
     def info(self, key: str) -> int:
@@ -284,8 +287,9 @@ class RadarCore:
         2 k_range_sq, 3 k_range_px; 1 retired), "window_saturations" / "word_saturations" (status
         words 2 / 3 of the last process() call; window_saturations is the sticky status_overflow
         of radar_core.vhd:447-456 as a count), "cfar2d_steps" (strip length of the last 2-D CFAR
-        launch)."""
-        k = {"chunk": L.INFO_CHUNK, "range_kernel": L.INFO_RANGE_KERNEL,
+        launch), "grid_range" ... "grid_k3c" (the handle's current bound on that kernel's workgroups;
+        a launch uses the smaller of it and its unit count)."""
+        k = {**{n: i for n, (_, i) in L.GRID_KEYS.items()}, "chunk": L.INFO_CHUNK, "range_kernel": L.INFO_RANGE_KERNEL,
              "window_saturations": L.INFO_WINDOW_SATURATIONS,
              "word_saturations": L.INFO_WORD_SATURATIONS, "cfar2d_steps": L.INFO_CFAR2D_STEPS}[key]
         v = C.c_int64(0)

@@ -81,7 +81,10 @@ extern "C" {
                                Still 8 with the plot extractor (fmcw_plots_*, fmcw_plot,
                                fmcw_plots_config): functions and types of its own were added, and
                                fmcw_config (29 words), FMCW_K_COUNT (4) and every existing
-                               signature are unchanged */
+                               signature are unchanged.
+                               Still 8 with the grid caps (FMCW_PARAM_GRID_*, FMCW_INFO_GRID_*) and
+                               fmcw_plots_set_grid_for_test: new enum values and one new function,
+                               no struct or signature change */
 
 typedef enum {
   FMCW_OK = 0,
@@ -229,13 +232,27 @@ typedef enum {
  * 1 (round 2's k_range2) is retired.  FMCW_INFO_WINDOW_SATURATIONS / FMCW_INFO_WORD_SATURATIONS:
  * status words 2 / 3 of the last fmcw_process call (fmcw_enqueue callers read them from
  * n_dets_dev).  FMCW_INFO_CFAR2D_STEPS: the strip length (workgroup steps) of the handle's last
- * 2-D CFAR launch (0 before the first). */
+ * 2-D CFAR launch (0 before the first).  FMCW_INFO_GRID_*: the handle's current bound on the
+ * workgroups of a persistent kernel (the FMCW_PARAM_GRID_* of the same name below): the grid
+ * computed at fmcw_create, or the cap set since.  A launch uses the smaller of this bound and its
+ * own unit count. */
 typedef enum { FMCW_INFO_CHUNK = 4, FMCW_INFO_RANGE_KERNEL = 6, FMCW_INFO_WINDOW_SATURATIONS = 7,
-               FMCW_INFO_WORD_SATURATIONS = 8, FMCW_INFO_CFAR2D_STEPS = 9 } fmcw_info_key;
+               FMCW_INFO_WORD_SATURATIONS = 8, FMCW_INFO_CFAR2D_STEPS = 9,
+               FMCW_INFO_GRID_RANGE = 10, FMCW_INFO_GRID_DOPPLER = 11, FMCW_INFO_GRID_CFAR2D = 12,
+               FMCW_INFO_GRID_K3B = 13, FMCW_INFO_GRID_K3C = 14 } fmcw_info_key;
 
 /* fmcw_set_param keys (tuning; results never depend on them).  FMCW_PARAM_CFAR2D_STEPS: steps
- * (4-wave-tile workgroup tiles) per 2-D CFAR strip, 0 = the library's cost model (default). */
-typedef enum { FMCW_PARAM_CFAR2D_STEPS = 1 } fmcw_param_key;
+ * (4-wave-tile workgroup tiles) per 2-D CFAR strip, 0 = the library's cost model (default).
+ * FMCW_PARAM_GRID_*: a cap on the workgroups of a persistent kernel, whose workgroups stride over
+ * their units whatever the grid: _RANGE the range stage (K1), _DOPPLER the Doppler stage (K2) and the
+ * stand-alone 1-D CFAR, _CFAR2D / _K3B / _K3C the three kernels of the 2-D CFAR.  Value 0 restores
+ * the grid computed at fmcw_create (occupancy x compute units; fixed grids for K3B / K3C), 1..2^20
+ * sets min(that grid, value); anything else is FMCW_EINVAL.  Fewer workgroups leave compute units
+ * to other streams' kernels.  The key and the value are checked before the handle.  A captured
+ * graph keeps the grids it was captured with: a cap set afterwards reaches only later calls and
+ * captures. */
+typedef enum { FMCW_PARAM_CFAR2D_STEPS = 1, FMCW_PARAM_GRID_RANGE = 2, FMCW_PARAM_GRID_DOPPLER = 3,
+               FMCW_PARAM_GRID_CFAR2D = 4, FMCW_PARAM_GRID_K3B = 5, FMCW_PARAM_GRID_K3C = 6 } fmcw_param_key;
 
 /* Status words of fmcw_enqueue / fmcw_cfar (n_dets_dev). */
 #define FMCW_STATUS_WORDS 4
@@ -406,6 +423,10 @@ int fmcw_plots_destroy(fmcw_plotter* p);   /* NULL is FMCW_OK */
 int fmcw_plots_enqueue(fmcw_plotter* p, const fmcw_det* dets_dev, size_t det_cap,
                        const uint32_t* n_dets_dev, fmcw_plot* plots_dev, size_t plot_cap,
                        uint32_t* n_plots_dev, void* stream);
+/* Test hook: bounds the workgroups of the plotter's two tile kernels (find, emit), which stride
+ * over the 1024-record tiles, so that a short list drives a workgroup through several tiles.
+ * 0 = the built-in bound (4096), else min(that bound, grid).  Plots never depend on it. */
+int fmcw_plots_set_grid_for_test(fmcw_plotter* p, uint32_t grid);
 
 /* ---- Track-while-scan tracker (host side) ----------------------------------------------
  * Replaces rtl/src/tws_tracker.vhd (radar_core.vhd:424-438): MAX_TRACKS alpha-beta tracks in

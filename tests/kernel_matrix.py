@@ -25,9 +25,14 @@ The 2-D CFAR (K3a / K3b / K3c, cfar2d.hpp) is mirrored down to the branches its 
 parameters, shape and strip length select (`cfar2d_select`), and runs as a stage of its own (group
 "cfar2d") on crafted maps (`cfar2d_layout`).  The strip length the cost model picks (cfar2d_steps 0)
 depends on the CU count and has no key; one case per Doppler size and window runs it.
+
+The persistent loops of K1, K2, k_cfar1d and K3 run one iteration per workgroup at these shapes; the
+cases "*-loop-g<grid>" repeat a case of the table under capped grids (Case.grid, fmcw_set_param's
+FMCW_PARAM_GRID_*) and claim a "<key>/loop" twin only where `loops` counts three iterations or more.
 """
 from __future__ import annotations
 
+import dataclasses
 import functools
 import itertools
 from dataclasses import dataclass
@@ -402,6 +407,135 @@ def range_family(c: Cfg, api: str = "process") -> int:
     return range_select(c.n_range, c.in_dtype, c.window, c.spectrum)[0]
 
 
+# ---- the persistent loops ------------------------------------------------------------------
+# K1, K2, k_cfar1d and K3a stride over their units with `for (g = blockIdx.x; g < n; g += gridDim.x)`
+# (kernels.hpp:373, :549, :710, :1370, :1627; cfar2d.hpp:539, :1143); K3b / K3c over candidates and
+# wave tiles per wave (cfar2d.hpp:1403, :1484).  The grids are occupancy x CUs (launch.hip
+# device_grids; 1024 for K3b / K3c), so at the shapes of this table a workgroup runs one iteration
+# unless the grid is capped (fmcw_set_param FMCW_PARAM_GRID_*, Case.grid).  A key "<key>/loop" says: a
+# case ran that kernel so that its busiest workgroup went through the loop at least LOOP_MIN times.
+LOOP_MIN = 3     # iteration 2 is the first to consume a prefetch issued inside the loop, iteration 3
+#                  the first that both consumes one and has issued one before it
+LOOP_GRIDS = (1, 2, 3, 16)
+MAX_CELLS = 2048 * 1024      # no case is larger than the "fast-xcd" shape: 2048 x 1024 x 1 frame
+
+
+def loopable(key: str, sym) -> bool:
+    """Keys that get a "/loop" twin: those that carry a kernel symbol, and K2's NCI, XCD-remap and
+    tile-order keys (the rx loop carries the prefetch into the next tile :1724; xcd_block_id :1432
+    and tile_fl :1526 decide which units a workgroup strides over)."""
+    return sym is not None or key.startswith(("k_doppler/nci<", "k_doppler/xcd-remap<")) or "/tile-order=" in key
+
+
+def loop_kernel(key: str) -> str:
+    """The kernel whose loop a loopable key belongs to."""
+    for prefix, kern in (("k_range", "k1"), ("k_doppler/xcd-remap<", "xcd"), ("k_doppler", "k2"),
+                         ("k_cfar1d<", "cfar1d"), ("k_cfar2d_decide<", "k3b"), ("k_cfar2d_emit<", "k3c"),
+                         ("k_cfar2d", "k3a")):
+        if key.startswith(prefix):
+            return kern
+    raise KeyError(key)
+
+
+def tiles_frame(c: Cfg) -> int:
+    """Wave tiles of a frame: n_range / WR, WR = 64 / P rows of P = NC / 16 lanes (kernels.hpp:997-998;
+    plan.hip tiles_frame)."""
+    return c.n_range // (64 // (c.n_doppler // 16))
+
+
+def k1_units(c: Cfg, nf: int) -> int:
+    """launch.hip:73: n_groups = nf * n_rx * (n_doppler / T) chirp groups per K1 launch."""
+    return nf * c.n_rx * (c.n_doppler // range_T(c.n_range))
+
+
+def tile_units(c: Cfg, nf: int) -> int:
+    """launch.hip:48-50 (K2 and k_cfar1d): ceil(nf * tiles_frame / WPB) workgroup steps, WPB = 4."""
+    return -(-nf * tiles_frame(c) // 4)
+
+
+def k3a_units(c: Cfg, nf: int, steps: int) -> int:
+    """launch.hip:110-113: nf * ceil(tpf / steps) strips, tpf = ceil(tiles_frame / 4)."""
+    return nf * len(cfar2d_strips(c.n_range, c.n_doppler, steps))
+
+
+def k3c_units(c: Cfg, nf: int) -> int:
+    """Wave tiles of a K3 launch (at most: k_cfar2d_emit takes those with candidates, cfar2d.hpp:1483),
+    shared by the 4 waves of each workgroup."""
+    return nf * tiles_frame(c)
+
+
+def wg_units(units: int, grid: int):
+    """The units each workgroup of a launch takes, in its order: the launch sites bound the grid by
+    the unit count (launch.hip:50, :78, :114), workgroup b takes b, b + grid, ..."""
+    g = min(units, grid)
+    return [list(range(b, units, g)) for b in range(g)]
+
+
+def busiest(units: int, grid: int) -> int:
+    """Iterations of the busiest workgroup; the last of them has no next unit (the loops end)."""
+    return max(map(len, wg_units(units, grid)), default=0)
+
+
+def k3a_walk(c: Cfg, nf: int, steps: int, grid: int):
+    """Per workgroup, the strips it takes as (frame, "down" / "up" / "one-step"): strip g is strip
+    g / nf of frame g % nf, odd strips walk upwards (cfar2d.hpp:542-557, :1144-1162)."""
+    per_frame = cfar2d_strips(c.n_range, c.n_doppler, steps)
+    out = []
+    for mine in wg_units(nf * len(per_frame), grid):
+        out.append([(g % nf, "one-step" if per_frame[g // nf][1] == 1 else "up" if (g // nf) & 1 else "down")
+                    for g in mine])
+    return out
+
+
+def k3a_turns(walk) -> bool:
+    """The K3a rule: some workgroup runs a down strip right after an up strip and an up strip right
+    after a down strip, on the LDS the other left behind; or, where every strip is one step (no
+    direction), strips of two different frames one after the other."""
+    for w in walk:
+        pairs = list(zip(w, w[1:]))
+        if all(d == "one-step" for _, d in w):
+            if any(a[0] != b[0] for a, b in pairs):
+                return True
+        elif (any(a[1] == "up" and b[1] == "down" for a, b in pairs)
+              and any(a[1] == "down" and b[1] == "up" for a, b in pairs)):
+            return True
+    return False
+
+
+def launch_frames(nf: int, chunk_frames: int):
+    """Frames of each K1 / K2 launch of one fmcw_process call (fmcw_api.hip:288-292); the auto chunk
+    holds every case of this table whole."""
+    ch = chunk_frames or nf
+    return [min(ch, nf - f0) for f0 in range(0, nf, ch)]
+
+
+def loops(group: str, c: Cfg, nf: int, grid: int, steps: int = 0, chunk_frames: int = 0) -> dict:
+    """{kernel: its busiest workgroup's iterations under a cap of `grid` workgroups} for the kernels
+    whose "/loop" keys a case may claim (at least LOOP_MIN in every launch of the call; "xcd" also
+    needs a launch grid that is a multiple of 8 and not 8 itself, else xcd_block_id is the identity:
+    (b & 7) * (grid >> 3) + (b >> 3) = b at grid 8; "k3a" also k3a_turns).  K3b's count depends on the data: a case claims it with its grid, and
+    test_kernel_matrix holds the oracle's detections of that case to 3 x 4 x grid."""
+    out = {}
+    if not grid:
+        return out
+    if group == "range":
+        out["k1"] = busiest(k1_units(c, nf), grid)
+    if group in ("process", "cfar1d"):
+        per = launch_frames(nf, chunk_frames)
+        out["k1"] = min(busiest(k1_units(c, n), grid) for n in per)
+        out["k2"] = min(busiest(tile_units(c, n), grid) for n in per)
+        if all(min(tile_units(c, n), grid) % 8 == 0 and min(tile_units(c, n), grid) > 8 for n in per):
+            out["xcd"] = out["k2"]
+    if group == "cfar1d":
+        out["cfar1d"] = busiest(tile_units(c, nf), grid)
+    if group == "cfar2d" and steps:
+        if k3a_turns(k3a_walk(c, nf, steps, grid)):
+            out["k3a"] = busiest(k3a_units(c, nf, steps), grid)
+        out["k3b"] = LOOP_MIN
+        out["k3c"] = -(-k3c_units(c, nf) // (4 * grid))
+    return {k: n for k, n in out.items() if n >= LOOP_MIN}
+
+
 def _cfar_options():
     yield "none", CFAR1D_SETS[0], CFAR2D_SETS[0], False
     for p in CFAR1D_SETS:
@@ -457,6 +591,8 @@ def reachable_with_symbols():
                 found.update(select(c, "range_ct"))
                 found.update(select(c, "cfar"))
     found.update(cfar2d_reachable())
+    # every configuration can be run with enough frames under a capped grid: all the twins are reachable
+    found.update({k + "/loop": None for k, sym in list(found.items()) if loopable(k, sym)})
     return found
 
 
@@ -489,15 +625,24 @@ class Case:
     seed: int = 1234
     steps: int = 0                    # the cfar2d_steps parameter (0: the cost model)
     chunk_frames: int = 0             # fmcw_config.chunk_frames (0: the library's choice)
+    grid: int = 0                     # 0: the library's grids; g > 0: all five FMCW_PARAM_GRID_* caps set to g
+
+    def selected(self):
+        if self.group == "range":
+            return select(self.cfg, "range_ct")
+        if self.group == "cfar2d":
+            return select(self.cfg, "cfar", self.steps)
+        if self.group == "cfar1d":
+            return select(self.cfg, "cfar") + select(self.cfg, "process")
+        return select(self.cfg, "process")
+
+    def loops(self) -> dict:
+        return loops(self.group, self.cfg, self.nf, self.grid, self.steps, self.chunk_frames)
 
     def keys(self) -> set:
-        if self.group == "range":
-            return variants(self.cfg, "range_ct")
-        if self.group == "cfar2d":
-            return variants(self.cfg, "cfar", self.steps)
-        if self.group == "cfar1d":
-            return variants(self.cfg, "cfar") | variants(self.cfg, "process")
-        return variants(self.cfg, "process")
+        sel = self.selected()
+        looping = self.loops()
+        return {k for k, _ in sel} | {k + "/loop" for k, sym in sel if loopable(k, sym) and loop_kernel(k) in looping}
 
 
 def _frames_for(ns):
@@ -673,6 +818,92 @@ def _build_cases():
     addi("q15-compat-same", 128, 2, "chain", "int_sat", n_rx=2, cfar="os1d")
     # the counters over two chunks of one call
     addi("q15-sat-chunked", 64, 3, "q15", "int_sat", nf=3, chunk_frames=2, n_rx=2, cfar="os1d")
+
+    # -- the persistent loops (the section above `loops`): cases of the table above once more under a
+    # capped grid, with the fewest frames at which the kernel they are for runs LOOP_MIN iterations in
+    # its busiest workgroup, and the largest of the grids 3, 2, 1 (16 for the XCD remap, which is the
+    # identity on grids that are no multiple of 8, and on 8) that still does.  Appended last, seeds 9000 and up.
+    base = {c.id: c for c in cases}
+    n_base = len(cases)
+
+    def loop(base_id, kernel, nf=0, grid=0, name="", **kw):
+        b = base[base_id]
+        seed = kw.pop("seed", 9000 + len(cases) - n_base + 1000 * LOOP_SEED_MOVED.get(base_id, 0))
+        want = ("k2", "xcd") if kernel == "xcd" else (kernel,)
+        grids = (grid,) if grid else (16,) if kernel == "xcd" else (3, 2, 1)
+        frames = (nf,) if nf else range(b.nf, 65)
+        for n in frames:        # the fewest frames first, then the largest grid
+            for g in grids:
+                c = dataclasses.replace(b, id=f"{b.id}{name}-loop-g{g}", nf=n, grid=g, seed=seed, **kw)
+                if set(want) <= set(c.loops()):
+                    assert c.cfg.n_range * c.cfg.n_doppler * c.cfg.n_rx * n <= max(MAX_CELLS, b.cfg.n_range * b.cfg.n_doppler * b.cfg.n_rx * b.nf), c.id
+                    assert c.id not in base, c.id
+                    cases.append(c)
+                    base[c.id] = c
+                    LOOP_BASE[c.id] = b.id
+                    return c
+        raise AssertionError((base_id, kernel, "no frame count up to 64 runs the loop"))
+
+    # K1 through fmcw_range_ct: every (N, input type) and the Q15 window
+    for ns in N_RANGE:
+        for dt in IN_DTYPES:
+            loop(f"range-{ns}-{dt}", "k1")
+        loop(f"range-{ns}-i16-q15", "k1")
+    # K1 through the whole path: the fused Doppler weight on every spectrum (fp16 and S48 stores), the
+    # fp16 store without it, the Q15 window (whose saturation count n_sat adds up over the groups)
+    for ns in N_RANGE:
+        for dt in IN_DTYPES:
+            for sp in SPECTRA:
+                loop(f"process-k1-{ns}-{dt}-{sp}", "k1")
+            loop(f"process-k1-{ns}-{dt}-f16-mti2", "k1")
+        loop(f"process-k1-{ns}-i16-q15", "k1")
+    # K2: for every K2 key with a twin that is still open, the first whole-path case of the table above
+    # that carries it (so every K2 symbol and addressing mode, both tile orders, every NCI and XCD
+    # key); then the picks by name below
+    open_keys = lambda: {k for k in reachable() if k.endswith("/loop")} - set().union(*(c.keys() for c in cases[n_base:]))  # noqa: E731
+    todo = open_keys()
+    for b in cases[:n_base]:
+        if b.group != "process" or b.recipe in ("int_clean", "int_sat"):
+            continue
+        mine = {k + "/loop" for k, sym in b.selected() if loopable(k, sym) and loop_kernel(k) in ("k2", "xcd")} & todo
+        if mine:
+            xcd = any(loop_kernel(k[:-5]) == "xcd" for k in mine)
+            # (a case the K1 lines above already run under a grid: once more, with the frames K2 needs)
+            todo -= loop(b.id, "xcd" if xcd else "k2", name="-k2" if any(i.startswith(b.id + "-loop-g") for i in base) else "").keys()
+    # NCI with an even and an odd n_rx on a prefetching kernel (pf = 16: FAST fp32, NC 64 / 128) and
+    # on one without (pf = 0: the generic MTI kernels, integer cases below; FAST at NC 1024)
+    for bid in ("process-k2-64-f32-fast-nrx2", "process-k2-128-f32-fast-nrx3", "process-k2-1024-f32-fast-nrx2",
+                "process-k2-64-s48-quad-fast-nrx3"):
+        if not any(i.startswith(bid + "-loop-g") for i in base):
+            loop(bid, "k2")
+    # the integer datapath: the counters add up over a workgroup's iterations (K1's n_sat over groups,
+    # K2's n_wsat / n_msat over tiles); one saturating Q15 and one saturating compat-MTI case (even and
+    # odd n_rx on kernels without a prefetch), and one in chunks of 2 of 4 frames, where every launch
+    # loops and the second starts at frame 2 (f0, tile0 non-zero)
+    loop("process-int-128-mti3-q15-sat", "k2")
+    loop("process-int-128-mti2-compat-sat", "k2")
+    # (n_rx 3; with its base's seed: INT_CLEAN_SHIFT is the smallest clean shift of that very cube)
+    loop("process-int-128-mti2-compat", "k2", seed=base["process-int-128-mti2-compat"].seed)
+    loop("process-int-128-mti3-q15-sat", "k2", nf=4, grid=1, name="-chunked", chunk_frames=2)
+    # k_cfar1d at every NC (the reference set; the cube of the same map drives K2 FAST as well)
+    for nc in N_DOPPLER:
+        loop(f"cfar1d-{nc}-ref8-g2-rank12-a4.0", "cfar1d")
+        loop(f"cfar1d-{nc}-compat", "cfar1d")
+    # K3 with strips of 3 (per frame: down, up, a short down strip; 3 frames, 9 strips): the generic
+    # kernel on (2, 1, 3, 1) under 1 workgroup, the level screen (k_cfar2d_lv at NC 1024) on the
+    # reference window under 2, rank 0 (dense: K3b's waves take hundreds of candidates each) under 3,
+    # compat (a kernel of its own at NC 1024) under 2; and strips of one step at NC 256 under 2 (grids
+    # that do not divide 3 frames: a workgroup's strips change frame)
+    for nc in N_DOPPLER:
+        ns = cfar2d_shape(nc)
+        w0, w1 = (".".join(map(str, w)) for w in CFAR2D_SETS[:2])
+        loop(f"cfar2d-{nc}x{ns}-w{w1}-steps3", "k3a", grid=1)
+        loop(f"cfar2d-{nc}x{ns}-w{w0}-steps3", "k3a", grid=2)
+        loop(f"cfar2d-{nc}x{ns}-w{w0}-rank0", "k3a", grid=3)
+        loop(f"cfar2d-{nc}x{ns}-w{w1}-rank0", "k3a", grid=3)
+        loop(f"cfar2d-{nc}x{ns}-w{w0}-compat", "k3a", grid=2)
+    for w in CFAR2D_SETS[:2]:
+        loop(f"cfar2d-256x128-w{'.'.join(map(str, w))}-steps1", "k3a", grid=2)
     return tuple(cases)
 
 
@@ -690,6 +921,20 @@ INT_CLEAN_SHIFT = {
 }
 
 
+# capped-grid cases (by their base's id) whose seed is moved on by 1000: fp16 spectrum with MTI on,
+# synth's random target near zero Doppler; the canceller removes it, and the format's rounding alone
+# (in fp64, no kernel) is then 4.4e-3 of what is left as the frame's peak
+# (test_kernel_matrix.test_case_is_fair_to_the_fp16_spectrum)
+# Likewise on the fp32 spectrum with the 3-pulse canceller: one frame's target is cancelled to 1 / 70
+# .. 1 / 600 of the other frames' peak, and K1's fp32 rounding of the uncancelled spectrum shows in
+# that frame's significant bins beyond 1e-4 (the phenomenon of INT_SEED_MOVED;
+# test_kernel_matrix.test_mti_case_keeps_every_frames_target).  "process-k2-64-s48-strided-gen": one
+# cell of 2 x 1024 x 64 lay 1.04e-4 of its threshold from it in the fp64 map, and the S48 map, itself
+# within 1e-4, decided it the other way (check_near_threshold allows 1e-4).  In all of these the
+# capped and the uncapped run gave the same bytes.
+LOOP_SEED_MOVED = {"process-k1-4096-f16-f16-mti2": 1, "process-k2-32-f32-mti3": 2, "process-k2-256-f32-mti3": 1,
+                   "process-k2-512-f32-mti3": 1, "process-k2-64-s48-strided-gen": 1}
+LOOP_BASE = {}          # id of a capped-grid case -> id of the case it repeats
 CASES = _build_cases()
 
 

@@ -38,6 +38,14 @@ def test_header_enums_match_binding():
     assert enum["FMCW_INFO_WORD_SATURATIONS"] == L.INFO_WORD_SATURATIONS
     assert enum["FMCW_INFO_CFAR2D_STEPS"] == L.INFO_CFAR2D_STEPS
     assert enum["FMCW_PARAM_CFAR2D_STEPS"] == L.PARAM_CFAR2D_STEPS
+    # the grid caps: five parameter keys after CFAR2D_STEPS, five info keys after 9, one name each
+    names = ("RANGE", "DOPPLER", "CFAR2D", "K3B", "K3C")
+    assert [enum[f"FMCW_PARAM_GRID_{n}"] for n in names] == [2, 3, 4, 5, 6]
+    assert [enum[f"FMCW_INFO_GRID_{n}"] for n in names] == [10, 11, 12, 13, 14]
+    assert list(L.GRID_KEYS) == [f"grid_{n.lower()}" for n in names]
+    for n in names:
+        assert L.GRID_KEYS[f"grid_{n.lower()}"] == (enum[f"FMCW_PARAM_GRID_{n}"], enum[f"FMCW_INFO_GRID_{n}"])
+    assert {v for k, v in enum.items() if k.startswith("FMCW_PARAM_")} == {1, 2, 3, 4, 5, 6}
     assert re.search(r"#define FMCW_ABI_VERSION 8\b", src)
     assert int(re.search(r"#define FMCW_STATUS_WORDS (\d+)", src).group(1)) == L.STATUS_WORDS
 
@@ -157,7 +165,28 @@ def test_fp16_spectrum_excludes_q15_window(lib_built):
 
 
 def test_set_param_rejects_bad_arguments(lib_built):
+    """The key and the value are checked before the handle, so the reject ranges hold without a
+    device: a grid cap outside 0..2^20 is FMCW_EINVAL with the key named; a good value then fails
+    on the null handle; an unknown key is FMCW_EINVAL."""
     assert lib_built.fmcw_set_param(None, L.PARAM_CFAR2D_STEPS, 4) == L.FMCW_EINVAL
+    for name, (param, info) in L.GRID_KEYS.items():
+        for bad in (-1, (1 << 20) + 1, 1 << 40, -(1 << 40)):
+            assert lib_built.fmcw_set_param(None, param, bad) == L.FMCW_EINVAL
+            assert name.encode() in lib_built.fmcw_last_error(), (name, bad)
+        for good in (0, 1, 1 << 20):
+            assert lib_built.fmcw_set_param(None, param, good) == L.FMCW_EINVAL
+            assert b"null handle" in lib_built.fmcw_last_error()
+        v = C.c_int64(-7)
+        assert lib_built.fmcw_get_info(None, info, C.byref(v)) == L.FMCW_EINVAL and v.value == -7
+    assert lib_built.fmcw_set_param(None, 7, 1) == L.FMCW_EINVAL
+    assert lib_built.fmcw_set_param(None, 0, 1) == L.FMCW_EINVAL
+
+
+def test_plots_grid_hook(lib_built):
+    """fmcw_plots_set_grid_for_test is exported (test_library_exports_every_symbol) and rejects a
+    null plotter."""
+    assert lib_built.fmcw_plots_set_grid_for_test(None, 1) == L.FMCW_EINVAL
+    assert b"plotter" in lib_built.fmcw_last_error()
 
 
 def test_release_library_reads_no_environment():

@@ -15,6 +15,12 @@ it, at every Doppler size and both cancellers, on int16 cubes that clip nowhere 
 clip at every stage.  Maps are held to the oracle's RTL arithmetic on the GPU's own range spectrum
 (1e-4; AMBM plus its two floor steps), detections bit-exact, and status words 2 and 3 exactly to the
 oracle's clip counts, which a second call on the same handle must reproduce.
+The persistent loops (cases "*-loop-g<grid>", kernel_matrix.loops): the same cases under
+fmcw_set_param's grid caps, so that a workgroup runs its loop three times and more -- the in-loop
+prefetch, the LDS reuse behind the loop head's barrier, the counters over iterations, K3a's ring on
+what the last strip left.  Same oracle, same bounds; then the same handle once more with the caps
+at 0: map, spectrum, records and status words must be the same bytes (fmcw.h: results never depend
+on tuning parameters).
 tests/test_kernel_matrix.py shows on the CPU that the table covers the dispatch rules and that a
 correct fp32 implementation passes every case that the C restatement can run.
 """
@@ -27,7 +33,7 @@ import cpu_backend as CB
 import fmcw_oracle as O
 import kernel_matrix as K
 from conftest import rel_err
-from fmcw import RadarCore
+from fmcw import DET_DTYPE, DeviceBuffer, RadarCore
 from test_gpu_parity import check_map, run_cfar_stage, run_range_ct
 
 pytestmark = pytest.mark.gpu
@@ -52,6 +58,57 @@ def make_core(c: K.Cfg, nf: int, **over):
     return RadarCore(**kw)
 
 
+GRIDS = ("grid_range", "grid_doppler", "grid_cfar2d", "grid_k3b", "grid_k3c")
+
+
+def cap_grids(core, case):
+    """Sets all five grid caps to case.grid (nothing for 0) and returns the created grids.  The
+    mirror's iteration counts (kernel_matrix.loops) assume the cap binds: every created grid is at
+    least the cap (grid_cfar2d is 0 on a handle without the 2-D CFAR)."""
+    if not case.grid:
+        return None
+    created = {k: core.info(k) for k in GRIDS}
+    print(f"{case.id}: created grids {created}, capped to {case.grid}")
+    for k in GRIDS:
+        core.set_param(k, case.grid)
+        assert core.info(k) == min(created[k], case.grid)
+        assert created[k] >= case.grid or (k == "grid_cfar2d" and case.cfg.cfar != "os2d" and created[k] == 0)
+    return created
+
+
+def uncap_grids(core, created):
+    for k in GRIDS:
+        core.set_param(k, 0)
+        assert core.info(k) == created[k]
+
+
+def run_stage_words(core, mag, cap):
+    """fmcw_cfar: (records, the four status words)."""
+    dm = DeviceBuffer(mag.nbytes)
+    dm.upload(np.ascontiguousarray(mag, np.float32))
+    dd = DeviceBuffer(cap * 16)
+    dn = DeviceBuffer(16)
+    core.cfar(dm, mag.shape[0], dd, cap, dn)
+    words = dn.download(np.uint32, (4,))
+    assert words[0] <= cap
+    out = dd.download(DET_DTYPE, (cap,))[:int(words[0])].copy()
+    for b in (dm, dd, dn):
+        b.free()
+    return out, [int(w) for w in words]
+
+
+def same_bytes(a, b):
+    assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+def same_process(a, b):
+    """Two fmcw_process outputs: map bytes, records, and the status words (word 1 is 0 in both:
+    fmcw_process fails on a non-zero one)."""
+    same_bytes(a.rd_map, b.rd_map)
+    same_bytes(a.dets, b.dets)
+    assert (a.n_dets, a.window_saturations, a.word_saturations) == (b.n_dets, b.window_saturations, b.word_saturations)
+
+
 @pytest.mark.parametrize("case", RANGE, ids=lambda c: c.id)
 def test_range_stage(gpu, case):
     """fmcw_range_ct on white full-scale noise vs O.range_ct (fp64): 1e-4 per (frame, rx), and 1e-4
@@ -59,8 +116,12 @@ def test_range_stage(gpu, case):
     c = case.cfg
     cube = K.make_cube(case)
     with make_core(c, case.nf) as core:
+        created = cap_grids(core, case)
         got = run_range_ct(core, cube, case.nf)
         assert core.info("range_kernel") == K.range_family(c)
+        if created:
+            uncap_grids(core, created)
+            same_bytes(run_range_ct(core, cube, case.nf), got)
     if c.window == "q15_rtl":
         ref = O.range_ct(O.window_q15_cube(cube), window=False)
     else:
@@ -101,6 +162,7 @@ def test_whole_path(gpu, case):
     else:
         cube, ref = K.reference(case)
     with make_core(c, case.nf) as core:
+        created = cap_grids(core, case)
         out = core.process(cube)
         if c.map_kind == "db":
             stage = None
@@ -108,12 +170,22 @@ def test_whole_path(gpu, case):
             stage = run_cfar_stage(core, out.rd_map, cap=out.rd_map.size)
         if q15:
             ref, e2e = _q15_reference(core, case, cube)
+        if created:
+            uncap_grids(core, created)
+            same_process(core.process(cube), out)
+            if stage is not None:
+                same_bytes(run_cfar_stage(core, out.rd_map, cap=out.rd_map.size), stage)
     assert out.rd_map.shape == (case.nf, c.n_range, c.n_doppler)
     if c.map_kind == "db":
         # test_db_map: the dB map against the oracle's log of the linear map of the same input
         with make_core(c, case.nf, map_kind="linear") as core:
+            created = cap_grids(core, case)
             lin = core.process(cube)
             lin_stage = run_cfar_stage(core, lin.rd_map, cap=lin.rd_map.size)
+            if created:
+                uncap_grids(core, created)
+                same_process(core.process(cube), lin)
+                same_bytes(run_cfar_stage(core, lin.rd_map, cap=lin.rd_map.size), lin_stage)
         np.testing.assert_allclose(out.rd_map, O.log_mag(lin.rd_map.astype(np.float64)), atol=2e-4)
         K.check_case_map(c, lin.rd_map, ref)
         want = K.oracle_dets(lin.rd_map, c)
@@ -140,15 +212,23 @@ def test_whole_path(gpu, case):
               f"worst gap/margin {frac:.3g}")
 
 
-def _run_integer(c, case, cube, **over):
-    """One handle: (process output, fmcw_cfar on its map, the range spectrum, a second process output)."""
+def _run_integer(c, case, cube, capped=False, **over):
+    """One handle: (process output, fmcw_cfar on its map, the range spectrum, a second process output).
+    `capped`: under the case's grid caps, and then, with the caps at 0, the same four once more: the
+    same bytes."""
     with make_core(c, case.nf, **over) as core:
+        created = cap_grids(core, case) if capped else None
         out = core.process(cube)
         stage = run_cfar_stage(core, out.rd_map, cap=out.rd_map.size)
         spec = run_range_ct(core, cube, case.nf)
         assert core.info("range_kernel") == K.range_family(c)
         assert core.info("chunk") == (over.get("chunk_frames") or case.nf)
         again = core.process(cube)
+        if created:
+            uncap_grids(core, created)
+            same_process(core.process(cube), out)
+            same_bytes(run_cfar_stage(core, out.rd_map, cap=out.rd_map.size), stage)
+            same_bytes(run_range_ct(core, cube, case.nf), spec)
     return out, stage, spec, again
 
 
@@ -179,7 +259,7 @@ def test_integer_path(gpu, case):
     ambm = c.magnitude == "ambm"
     cube = K.make_cube(case)
     over = dict(chunk_frames=case.chunk_frames) if case.chunk_frames else {}
-    out, stage, spec, again = _run_integer(c, case, cube, **over)
+    out, stage, spec, again = _run_integer(c, case, cube, capped=True, **over)
     assert out.rd_map.shape == (case.nf, c.n_range, c.n_doppler)
     ref = K.int_map(c, spec)
     worst_frame = worst_bin = 0.0
@@ -233,9 +313,17 @@ def test_cfar1d_stage_and_fused(gpu, case):
     m = K.cfar1d_map(case)
     cube = K.cube_from_map(m)
     with make_core(c, case.nf) as core:
-        stage = run_cfar_stage(core, m, cap=m.size)
+        created = cap_grids(core, case)
+        stage, words = run_stage_words(core, m, cap=m.size)
+        assert words[1] == 0
         out = core.process(cube)
         again = run_cfar_stage(core, out.rd_map, cap=m.size)
+        if created:
+            uncap_grids(core, created)
+            stage0, words0 = run_stage_words(core, m, cap=m.size)
+            same_bytes(stage0, stage)
+            assert words0 == words
+            same_process(core.process(cube), out)
     want, _, _ = K.cfar1d_oracle(m, c)
     np.testing.assert_array_equal(stage, want)
     # the fused kernel saw its own fp32 map: close to m, and decided exactly as the oracle on it
@@ -260,10 +348,17 @@ def test_cfar2d_stage(gpu, case):
     with make_core(c, case.nf, **over) as core:
         if case.steps:
             core.set_param("cfar2d_steps", case.steps)
-        got = run_cfar_stage(core, m, cap=m.size)          # asserts dropped == 0
+        created = cap_grids(core, case)
+        got, words = run_stage_words(core, m, cap=m.size)
+        assert words[1] == 0                               # nothing dropped
         if case.steps:
             per_frame = -(-c.n_range // K.cfar2d_TR(c.n_doppler))
             assert core.info("cfar2d_steps") == min(case.steps, per_frame)
+        if created:
+            uncap_grids(core, created)
+            got0, words0 = run_stage_words(core, m, cap=m.size)
+            same_bytes(got0, got)
+            assert words0 == words
     if c.compat_cfar:
         want, _, _ = K.cfar2d_oracle(m, c)
     else:

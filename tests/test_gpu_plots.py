@@ -6,6 +6,7 @@ order and the count exact; sum_mag within 1e-5 relative (<= 81 positive fp32 ter
 = 4.8e-6 in any order); d_range / d_doppler within 1e-4 bins (81 * 2^-24 * 4 for the numerator
 plus 4 * 4.8e-6 for the division, about 4e-5).
 """
+import functools
 import subprocess
 import sys
 
@@ -145,6 +146,57 @@ def test_plot_cap_shorter_than_count(gpu):
         assert np.all(rest == SENTINEL)
         # extract() retries once with the reported count
         assert_plots_match(px.extract(dets, plot_cap=cap), want)
+
+
+@functools.lru_cache(maxsize=None)
+def _larger(win):
+    dets = random_list(12, 2, 256, 128, 0.5)
+    want = plots_ref(dets, 256, 128, *win)
+    for a in (dets, want):
+        a.setflags(write=False)
+    return dets, want
+
+
+@pytest.mark.parametrize("win", [(1, 1), (4, 4)])
+def test_capped_grid_larger_list(gpu, win):
+    """k_plots_find and k_plots_emit stride over the 1024-record tiles with up to 4096 workgroups, so a
+    workgroup takes a second tile only beyond 4.2 M records.  test_larger_lists' list (about 32 tiles)
+    under 1 and 3 workgroups (fmcw_plots_set_grid_for_test: every tile after another on the same
+    staging arrays; 3 does not divide the tile count): the reference's plots, and the same bytes as
+    under the built-in grid, the sentinel beyond the plots included."""
+    dets, want = _larger(win)
+    assert len(dets) > 30 * 1024
+    with PlotExtractor(256, 128, win=win, max_dets=len(dets)) as px:
+        st0, got0, rest0 = run(px, dets)
+        assert list(st0) == [len(want), 0]
+        assert_plots_match(got0, want)
+        for grid in (1, 3, 0):
+            px.set_grid_for_test(grid)
+            st, got, rest = run(px, dets)
+            assert list(st) == [len(want), 0], grid
+            assert_plots_match(got, want)
+            assert got.tobytes() == got0.tobytes() and rest.tobytes() == rest0.tobytes(), grid
+            assert np.all(rest == SENTINEL)
+
+
+def test_capped_grid_plot_cap_shorter_than_count(gpu):
+    """test_plot_cap_shorter_than_count's list (two tiles) under 1 and 3 workgroups: the first
+    plot_cap plots, nothing stored beyond them (a later tile's offset is past plot_cap: k_plots_emit
+    leaves its loop), byte for byte what the built-in grid writes."""
+    dets = random_list(13, 3, 64, 32, 0.3)
+    want = plots_ref(dets, 64, 32, 1, 1)
+    assert len(dets) > 1024
+    cap = len(want) // 3
+    with PlotExtractor(64, 32, max_dets=len(dets)) as px:
+        st0, got0, rest0 = run(px, dets, plot_cap=cap)
+        for grid in (1, 3):
+            px.set_grid_for_test(grid)
+            st, got, rest = run(px, dets, plot_cap=cap)
+            assert list(st) == [len(want), 0] == list(st0)
+            assert_plots_match(got, want[:cap])
+            assert np.all(rest == SENTINEL)
+            assert got.tobytes() == got0.tobytes() and rest.tobytes() == rest0.tobytes()
+            assert_plots_match(px.extract(dets, plot_cap=cap), want)
 
 
 def test_truncated_input(gpu):

@@ -20,6 +20,7 @@ PROCESS = [c for c in K.CASES if c.group == "process"]
 CFAR1D = [c for c in K.CASES if c.group == "cfar1d"]
 CFAR2D = [c for c in K.CASES if c.group == "cfar2d"]
 INTEGER = [c for c in PROCESS if c.recipe in ("int_clean", "int_sat")]
+LOOPS = [c for c in K.CASES if c.grid]
 
 
 def test_case_ids_unique_and_legal():
@@ -99,6 +100,136 @@ def test_issue_variants_are_explicit_cases():
                     ("q15_rtl", False, "int_clean", "abs", False), ("q15_rtl", False, "int_sat", "abs", False),
                     ("q15_rtl", True, "int_clean", "ambm", True)} <= got
     assert any(c.chunk_frames and c.nf > c.chunk_frames and c.recipe == "int_sat" for c in INTEGER)
+    # the persistent loops: one key per kernel family and addressing mode, both XCD forms, K3 at the
+    # smallest and the largest Doppler size
+    for key in ("k_range<64,LoadF32,false,0>/cw=0/loop", "k_range<2048,LoadI16,true,0>/cw=0/loop",
+                "k_range<512,LoadF16,false,1>/cw=1/loop", "k_range<256,LoadI16,false,1>/cw=0/loop",
+                "k_range<128,LoadF32,false,2>/cw=1/loop", "k_range<1024,LoadI16,false,4>/cw=1/loop",
+                "k_range<2048,LoadF16,false,5>/cw=1/loop", "k_range_sq<4096,LoadI16,16,1,3,0>/cw=1/loop",
+                "k_range_sq<4096,LoadF32,16,1,3,5>/cw=1/loop", "k_range_px<LoadF16,4,4,0>/cw=0/loop",
+                "k_range_px<LoadI16,4,6,5>/cw=1/loop",
+                "k_doppler<32,mti=0,F32,FAST>/pf=16/per-point/loop", "k_doppler<32,mti=0,F16,GEN>/pf=16/uniform/loop",
+                "k_doppler<256,mti=0,F32,FAST>/pf=16/uniform/loop", "k_doppler<512,mti=0,F32,GEN>/pf=8/uniform/loop",
+                "k_doppler<1024,mti=0,F32,FAST>/pf=0/loop", "k_doppler<64,mti=2,F32,GEN>/pf=0/loop",
+                "k_doppler<1024,mti=3,F16,GEN>/pf=0/loop", "k_doppler<64,mti=0,S48,FAST>/pf=16/per-point/loop",
+                "k_doppler<128,mti=0,S48,GEN>/pf=16/uniform/loop", "k_doppler<256,mti=0,S48S,FAST>/pf=16/strided/loop",
+                "k_doppler<512,mti=0,S48PS,GEN>/pf=8/strided/loop", "k_doppler<1024,mti=0,S48S,FAST>/pf=0/loop",
+                "k_doppler/nci<pf=16,F32>/loop", "k_doppler/nci<pf=8,F16>/loop", "k_doppler/nci<pf=0,F32>/loop",
+                "k_doppler/nci<pf=16,S48>/loop", "k_doppler/nci<pf=16,S48S>/loop", "k_doppler/nci<pf=0,S48PS>/loop",
+                "k_doppler/xcd-remap<NC=1024,B=8,T=2>/loop", "k_doppler/xcd-remap<NC=1024,B=6,T=4>/loop",
+                "k_doppler/xcd-remap<NC=1024,B=6,T=2>/loop", "k_doppler/xcd-remap<NC=512,B=6,T=2>/loop",
+                "k_doppler<32>/tile-order=frame-minor/loop", "k_doppler<32>/tile-order=grouped/loop",
+                "k_doppler<1024>/tile-order=grouped/loop",
+                "k_cfar1d<32>/loop", "k_cfar1d<1024>/loop",
+                "k_cfar2d<32,0,0,0,0>/loop", "k_cfar2d<32,6,2,5,1>/loop", "k_cfar2d<1024,0,0,0,0>/loop",
+                "k_cfar2d_lv<1024,5,1,false>/loop", "k_cfar2d_lv<1024,5,1,true>/loop",
+                "k_cfar2d_decide<32>/loop", "k_cfar2d_decide<1024>/loop", "k_cfar2d_emit<32>/loop",
+                "k_cfar2d_emit<1024>/loop"):
+        assert key in covered, key
+    # every loop case is a case of the table above with a grid of 1, 2, 3 or 16 (and more frames);
+    # nothing is larger than 2048 x 1024 x 1 frame unless its base case already was
+    by_id = {c.id: c for c in K.CASES}
+    for c in LOOPS:
+        b = by_id[K.LOOP_BASE[c.id]]
+        assert not b.grid and c.grid in K.LOOP_GRIDS and c.cfg == b.cfg and (c.group, c.recipe, c.steps) == (b.group, b.recipe, b.steps)
+        assert c.nf >= b.nf and (c.seed >= 9000 or c.recipe == "int_clean" and c.seed == b.seed) and c.id.endswith(f"-loop-g{c.grid}")
+        cells = lambda x: x.cfg.n_range * x.cfg.n_doppler * x.cfg.n_rx * x.nf  # noqa: E731
+        assert cells(c) <= max(K.MAX_CELLS, cells(b)), c.id
+    sat = [c for c in LOOPS if c.recipe == "int_sat"]
+    assert any(c.cfg.window == "q15_rtl" for c in sat) and any(c.cfg.compat_mti and c.cfg.window == "hamming" for c in sat)
+    # the chunked one: every launch of the call loops, and the second starts beyond frame 0
+    assert any(c.chunk_frames and K.launch_frames(c.nf, c.chunk_frames) == [c.chunk_frames] * 2 for c in sat)
+    # NCI under a capped grid: an even and an odd n_rx on kernels with and without a prefetch
+    nci = {(K.k2_prefetch(c.cfg.n_doppler, c.cfg.mti) > 0, c.cfg.n_rx % 2) for c in LOOPS
+           if c.group == "process" and c.cfg.n_rx > 1 and "k2" in c.loops()}
+    assert nci == {(True, 0), (True, 1), (False, 0), (False, 1)}
+    for nc in K.N_DOPPLER:          # K3a: the generic, the level-screen / lv and the compat kernel, strips of 3
+        got = {(c.cfg.cfar2d, c.cfg.compat_cfar) for c in LOOPS if c.group == "cfar2d" and c.cfg.n_doppler == nc
+               and c.steps == 3 and "k3a" in c.loops()}
+        assert {(K.CFAR2D_SETS[0], False), (K.CFAR2D_SETS[1], False), (K.CFAR2D_SETS[0], True)} <= got
+
+
+def _stride(units, grid):
+    """The loop as the kernels write it: for (g = blockIdx.x; g < units; g += gridDim.x), under the
+    launch sites' grid of min(units, cap)."""
+    n = min(units, grid)
+    return [[g for g in range(b, units, n)] for b in range(n)]
+
+
+@pytest.mark.parametrize("case", LOOPS, ids=lambda c: c.id)
+def test_loop_case_runs_its_loops(case):
+    """Every "/loop" key a case claims, recomputed here from the unit counts of the launch sites and
+    the loops as the kernels write them: the busiest workgroup runs at least 3 iterations in every
+    launch of the call, and its last has no next unit.  K2 per wave (tile = bid WPB + wave, step grid
+    WPB, kernels.hpp:1627), with the XCD remap a permutation that is not the identity; K3a with a down
+    strip right after an up strip and an up strip right after a down strip in one workgroup (strips of
+    one step: two frames in a row); K3c per wave of the 4 grid waves.  A case with a grid claims at
+    least one such key."""
+    c, G = case.cfg, case.grid
+    claimed = {k[:-5] for k in case.keys() if k.endswith("/loop")}
+    assert claimed, "a capped grid that loops nowhere"
+    assert all(k in case.keys() for k in claimed)
+    kernels = {K.loop_kernel(k) for k in claimed}
+    T = 16 if c.n_range <= 128 else 8 if c.n_range <= 512 else 4 if c.n_range == 1024 else 2    # kernels.hpp:295
+    wr = 64 // (c.n_doppler // 16)                                                                # :997-998
+    per_launch = K.launch_frames(case.nf, case.chunk_frames) if case.group in ("process", "cfar1d") else [case.nf]
+    assert sum(per_launch) == case.nf and (not case.chunk_frames or max(per_launch) == case.chunk_frames < case.nf)
+    if "k1" in kernels:
+        for n in per_launch:
+            walks = _stride(n * c.n_rx * c.n_doppler // T, G)                                   # launch.hip:73
+            assert max(map(len, walks)) >= 3
+            assert all(w[-1] + len(walks) >= n * c.n_rx * c.n_doppler // T for w in walks)
+    if kernels & {"k2", "xcd", "cfar1d"}:
+        for n in per_launch:
+            n_tiles = n * (c.n_range // wr)                                                      # launch.hip:49
+            grid = min(-(-n_tiles // 4), G)                                                      # :50
+            per_wave = []
+            for b in range(grid):
+                remap = "xcd" in kernels and grid % 8 == 0
+                bid = (b & 7) * (grid >> 3) + (b >> 3) if remap else b                           # kernels.hpp:1432-1435
+                per_wave += [list(range(bid * 4 + wv, n_tiles, grid * 4)) for wv in range(4)]
+            assert sorted(t for w in per_wave for t in w) == list(range(n_tiles))               # every tile once
+            assert max(map(len, per_wave)) >= 3
+            assert all(w[-1] + grid * 4 >= n_tiles for w in per_wave if w)
+            if "xcd" in kernels:     # a grid of 8 is a multiple of 8 too, but maps every block to itself
+                assert grid % 8 == 0
+                assert [(b & 7) * (grid >> 3) + (b >> 3) for b in range(grid)] != list(range(grid))
+    if kernels & {"k3a", "k3b", "k3c"}:
+        assert case.group == "cfar2d" and case.steps
+        tr = 4 * wr                                                                              # cfar2d.hpp:106
+        tpf = -(-c.n_range // tr)                                                                # launch.hip:110
+        steps = min(case.steps, tpf)
+        spf = -(-tpf // steps)
+        walks = _stride(case.nf * spf, G)                                                        # launch.hip:113-114
+        if "k3a" in kernels:
+            assert max(map(len, walks)) >= 3
+            ok = False
+            for w in walks:
+                seq = []
+                for g in w:
+                    f, i = g % case.nf, g // case.nf                                             # cfar2d.hpp:542-543
+                    n_steps = min(i * steps + steps, tpf) - i * steps
+                    seq.append((f, None if n_steps == 1 else bool(i & 1)))                       # :554, :557
+                pairs = list(zip(seq, seq[1:]))
+                if all(d is None for _, d in seq):
+                    ok |= any(a[0] != b[0] for a, b in pairs)
+                else:
+                    ok |= (any(a[1] is True and b[1] is False for a, b in pairs)
+                           and any(a[1] is False and b[1] is True for a, b in pairs))
+            assert ok
+        if "k3c" in kernels:
+            assert -(-case.nf * (c.n_range // wr) // (4 * G)) >= 3
+
+
+@pytest.mark.parametrize("case", [c for c in LOOPS if c.group == "cfar2d"], ids=lambda c: c.id)
+def test_cfar2d_loop_case_has_candidates(case):
+    """K3b strides over the candidates, 4 waves per workgroup and one candidate per wave at a time
+    (cfar2d.hpp:1403-1428); their number depends on the data, and every detection was a candidate.
+    The oracle's detections on the case's map, all in one launch (3 frames), are at least 3 per wave
+    of the capped grid."""
+    dets, _, _ = _oracle2d(case)
+    assert case.nf == 3
+    assert len(dets) >= 3 * 4 * case.grid, len(dets)
 
 
 def _kernel_symbols(tmp_path):
@@ -151,6 +282,39 @@ def test_case_is_fair_to_fp32(case):
     fp32 = dataclasses.replace(c, spectrum="f32")
     K.check_case_map(fp32, got, ref)
     K.check_near_threshold(dets, ref, fp32)
+
+
+def _fp16(z):
+    return z.real.astype(np.float16).astype(np.float64) + 1j * z.imag.astype(np.float16).astype(np.float64)
+
+
+@pytest.mark.parametrize("case", [c for c in PROCESS if c.cfg.spectrum == "f16" and c.cfg.magnitude == "abs"],
+                         ids=lambda c: c.id)
+def test_case_is_fair_to_the_fp16_spectrum(case):
+    """The fp16 spectrum's rule is 2e-3 of the frame's peak.  The format alone, applied in fp64 to the
+    oracle's range spectrum (half2(X / N_range), fmcw.h FMCW_SPEC_F16), must leave the case's map
+    within 1.9e-3 (the rest is the fp32 arithmetic's 1e-4): with MTI on, a target near zero Doppler
+    is cancelled, the frame's peak falls to the clutter's level, and no implementation of the format
+    meets the rule on that cube (kernel_matrix.LOOP_SEED_MOVED)."""
+    c = case.cfg
+    cube, ref = K.reference(case)
+    for f in range(case.nf):
+        spec = O.range_ct(K.to_complex(cube[f], c.in_dtype)) * 2.0 ** -c.range_shift
+        rd = O.doppler_stage(_fp16(spec / c.n_range) * c.n_range, mti_mode=c.mti)
+        e = np.abs(O.magnitude(rd, rx_axis=0) - ref[f]).max() / ref[f].max()
+        assert e <= 1.9e-3, f"frame {f}: the format alone moves the map by {e:.3g} of its peak"
+
+
+@pytest.mark.parametrize("case", [c for c in LOOPS if c.group == "process" and c.cfg.mti == 3 and c.cfg.window == "hamming"
+                                  and c.cfg.spectrum == "f32" and c not in INTEGER], ids=lambda c: c.id)
+def test_mti_case_keeps_every_frames_target(case):
+    """The 3-pulse canceller removes a target near zero Doppler, and its frame's peak falls to the
+    clutter's level, where K1's fp32 rounding of the uncancelled spectrum shows beyond the per-bin
+    1e-4 (seen at 1 / 70 of the other frames' peak and below; kernel_matrix.LOOP_SEED_MOVED).  Every
+    frame's peak in the fp64 oracle's map is within a factor of 32 of the case's largest."""
+    _, ref = K.reference(case)
+    peaks = [float(ref[f].max()) for f in range(case.nf)]
+    assert min(peaks) >= max(peaks) / 32, peaks
 
 
 @pytest.mark.parametrize("case", CFAR1D, ids=lambda c: c.id)
