@@ -1,7 +1,7 @@
 // cfar2d.hpp -- K3: 2-D OS-CFAR (rtl/src/os_cfar_2d.vhd:140-217) over the linear magnitude
-// map, for gfx950.  Included from inside namespace fmcw by kernels.hpp (uses DetSink,
-// det_reserve_wave, wave_excl_scan, lt_bit, opaque, nonneg / q17, MH and DopplerGeom declared
-// there).
+// map, for gfx950.  Uses DetSink (kernel_types.hpp, where Cfar2DArgs and Cfar2Cands also live),
+// det_reserve_wave, wave_excl_scan, lt_bit, nonneg / q17 (det_sink.hpp), MH and DopplerGeom
+// (cfar1d.hpp) and opaque (fft_device.hpp).
 //
 // Tiles.  The detection unit is K2's wave tile: WR = 1024/NC range rows x NC Doppler cells
 // (16 cells per lane), so the 1-D and 2-D CFAR share one sink layout and one (frame, range,
@@ -24,30 +24,15 @@
 //     reserves its sink range, pass 2 walks its detections again and finds the exact ranked
 //     value by a pivoting select (threshold = fl(s * ranked), dbg_threshold).
 #pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
 
-struct Cfar2DArgs {
-  int hr, gr, hd, gd;  // half extents (ref + guard) and guards, range / Doppler
-  int n_ref, rank;
-  float s_min, sc_min, sc_nom, sc_max;
-  int override_;
-  int compat;          // FMCW_COMPAT_CFAR: 17-bit integer cells, integer mean and brackets
-};
+#include "cfar1d.hpp"
+#include "det_sink.hpp"
+#include "fft_device.hpp"
+#include "kernel_types.hpp"
 
-// The candidate list of one 2-D CFAR launch (capacity: every cell of the launch, so it cannot
-// overflow): cell[i] = (frame in the launch x ns + range) x NC + doppler, runs of one wave tile in
-// cell order; thr[i] = the threshold of a detection, -1 for a rejected candidate (k_cfar2d_decide);
-// tiles[] = the wave tiles with candidates; ctr[0] = candidates, ctr[1] = such tiles (zeroed before
-// the launch).
-struct Cfar2Cands {
-  uint32_t* cell;
-  float* thr;
-  uint32_t* tiles;
-  uint32_t* ctr;
-  // k_cfar2d_lv's strip-private spill regions (room for every cell / wave tile of the launch: a
-  // strip's part starts at its first cell / wave tile), copied into cell / tiles at the strip's end
-  uint32_t* pcell;
-  uint32_t* ptile;   // 2 words per wave tile
-};
+namespace fmcw {
 
 // 7-bit keys.  key(v) = clamp((bits(v) >> SH) - base, 0, 127) for a non-negative fp32 cell v:
 // 2^(23 - SH) levels per octave (16 at SH = 19) over a 128-level window that starts `base`
@@ -1542,3 +1527,5 @@ k_cfar2d_emit(const float* __restrict__ map, int ns, int frame0, Cfar2DArgs a, C
     }
   }
 }
+
+}  // namespace fmcw

@@ -3,6 +3,7 @@
 // handle's per-call counters; k_zero_words arms them where no k_det_list did.
 #include <algorithm>
 
+#include "det_sink.hpp"
 #include "handle.hpp"
 
 namespace fmcw {

@@ -1,11 +1,13 @@
 // dispatch.hpp -- kernel selection tables of libfmcw.so.  Each table lives in its own
 // translation unit (inst_*.hip) so the template instantiations compile in parallel; the host
-// logic (plan.hip build_plan, once per handle) sees only these function-pointer factories.
+// logic (plan.hip build_plan, once per handle) sees only these function-pointer factories and the
+// argument structs of kernel_types.hpp: no kernel body.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
-#include "kernels.hpp"
+#include "kernel_types.hpp"
 
 namespace fmcw {
 
@@ -38,18 +40,9 @@ DopplerFn doppler_fn_f16(uint32_t nc, int mti, bool fast);            // inst_do
 enum S48Form { kS48Quad = 0, kS48Pair = 1, kS48Strided = 2 };
 inline int s48_form(int range_T) { return range_T == 2 ? kS48Pair : range_T == 4 ? kS48Strided : kS48Quad; }
 DopplerFn doppler_fn_s48(uint32_t nc, int mti, bool fast, int form);
-inline DopplerInfo doppler_info(uint32_t nc, int mti = FMCW_MTI_OFF, int spec = FMCW_SPEC_F32, bool fast = false,
-                                bool q15 = false, int range_T = 4) {
-  DopplerFn fn = spec == FMCW_SPEC_F16   ? doppler_fn_f16(nc, mti, fast)
-                 : spec == FMCW_SPEC_S48 ? doppler_fn_s48(nc, mti, fast, s48_form(range_T))
-                                         : doppler_fn_f32(nc, mti, fast, q15);
-  switch (nc) {
-#define D_(N) case N: return {fn, DopplerGeom<N>::WR, DopplerGeom<N>::NT};
-    D_(32) D_(64) D_(128) D_(256) D_(512) D_(1024)
-#undef D_
-  }
-  return {nullptr, 0, 0};
-}
+// inst_doppler.hip (the geometry is DopplerGeom's, cfar1d.hpp)
+DopplerInfo doppler_info(uint32_t nc, int mti = FMCW_MTI_OFF, int spec = FMCW_SPEC_F32, bool fast = false,
+                         bool q15 = false, int range_T = 4);
 
 // ---- stand-alone 1-D CFAR (fmcw_cfar) and K3 2-D CFAR ---------------------------------------
 using Cfar1Fn = void (*)(const float*, int, int, int, int, Cfar1DArgs, DetSink);

@@ -43,7 +43,7 @@ struct fmcw_handle {
   size_t stage_dets_cap = 0;
   int cfar2_steps = 0;                  // 2-D CFAR steps per strip (0 = cost model; FMCW_PARAM_CFAR2D_STEPS)
   int cfar2_steps_last = 0;             // the strip length of the last 2-D CFAR launch (FMCW_INFO_CFAR2D_STEPS)
-  // 2-D CFAR candidate lists (cfar2d.hpp Cfar2Cands): room for every cell of plan.k3_frames frames,
+  // 2-D CFAR candidate lists (kernel_types.hpp Cfar2Cands): room for every cell of plan.k3_frames frames,
   // and a counter pair per K3 launch of a call (plan.k3_launches of them, zeroed with the status words)
   uint32_t* cand_cell = nullptr;
   float* cand_thr = nullptr;

@@ -1,4 +1,5 @@
 // inst_cfar2.hip -- K3 (2-D OS-CFAR) instantiations, see dispatch.hpp.
+#include "cfar2d.hpp"
 #include "dispatch.hpp"
 
 namespace fmcw {

@@ -1,6 +1,7 @@
 // inst_doppler_h16.hip -- K2 instantiations on the fp16 corner-turned spectrum
 // (FMCW_SPEC_F16), see dispatch.hpp.
 #include "dispatch.hpp"
+#include "doppler_kernel.hpp"
 
 namespace fmcw {
 namespace {

@@ -1,9 +1,10 @@
 // inst_doppler_s48.hip -- K2 instantiations on the S48 corner-turned spectrum (FMCW_SPEC_S48,
-// kernels.hpp s48_pack / s48_unpack), quad (T >= 8), strided-quad (T = 4) or pair (T = 2) form,
+// spectrum.hpp s48_pack / s48_unpack), quad (T >= 8), strided-quad (T = 4) or pair (T = 2) form,
 // see dispatch.hpp.
 // MTI off only (its neighbours in slow time belong to other lanes of the exponent group);
 // n_doppler >= 64.
 #include "dispatch.hpp"
+#include "doppler_kernel.hpp"
 
 namespace fmcw {
 namespace {

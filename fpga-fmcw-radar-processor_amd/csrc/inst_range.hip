@@ -1,5 +1,6 @@
 // inst_range.hip -- K1 instantiations (window + range FFT + corner turn), see dispatch.hpp.
 #include "dispatch.hpp"
+#include "range_kernels.hpp"
 
 namespace fmcw {
 namespace {
@@ -50,7 +51,7 @@ RangeInfo range_sq(int dtype, int spec) {
   return {fn, SqGeom<N, S::V>::T, SqGeom<N, S::V>::RB, NT, kRangeSeq};
 }
 
-// k_range_px (round 3): N = 8192, two LDS exchanges + a permlane radix-2 (kernels.hpp).  The S48
+// k_range_px (round 3): N = 8192, two LDS exchanges + a permlane radix-2 (range_kernels.hpp).  The S48
 // instantiation keeps 6 of its 16 range-window values in LDS (fp32: 4): with 4 the S48 packing
 // spills 12 B per lane at 128 VGPRs, with 6 none (fp16 / int16 input)
 template <int SP>

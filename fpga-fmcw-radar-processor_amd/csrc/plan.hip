@@ -11,7 +11,7 @@ namespace {
 
 bool pow2(uint32_t x) { return x && !(x & (x - 1)); }
 
-// K2's FAST instantiation (kernels.hpp): MTI off, |X| magnitude, no dB map, fp32 windows, and the
+// K2's FAST instantiation (doppler_kernel.hpp): MTI off, |X| magnitude, no dB map, fp32 windows, and the
 // 1-D CFAR (if any) at the reference geometry in fp32
 bool k2_fast(const fmcw_config& c) {
   const bool cfar_ok = c.cfar_kind != FMCW_CFAR_OS1D ||

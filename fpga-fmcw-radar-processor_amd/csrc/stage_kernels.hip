@@ -1,4 +1,5 @@
 // stage_kernels.hip -- the small kernels of the stage entry points (fmcw_range_ct, fmcw_magnitude).
+#include "cfar1d.hpp"
 #include "handle.hpp"
 
 namespace fmcw {

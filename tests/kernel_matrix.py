@@ -40,7 +40,7 @@ from dataclasses import dataclass
 import numpy as np
 
 N_RANGE = (64, 128, 256, 512, 1024, 2048, 4096, 8192)     # dispatch.hpp / inst_range.hip R_()
-N_DOPPLER = (32, 64, 128, 256, 512, 1024)                  # dispatch.hpp doppler_info D_()
+N_DOPPLER = (32, 64, 128, 256, 512, 1024)                  # inst_doppler.hip doppler_info D_()
 N_RX = (1, 2, 3)                                           # one, even, odd (the rx loop of k_doppler)
 IN_DTYPES = ("f32", "f16", "i16")
 WINDOWS = ("hamming", "q15_rtl")
@@ -64,10 +64,10 @@ CFAR2D_RANK_PCT = (0, 75, 100)
 CFAR2D_OVERRIDE = (0, 3)
 CFAR2D_STEPS = (1, 3, 5)
 
-SP_NAME = {0: "F32", 1: "F16", 2: "S48", 4: "S48S", 5: "S48PS"}   # kernels.hpp:127
+SP_NAME = {0: "F32", 1: "F16", 2: "S48", 4: "S48S", 5: "S48PS"}   # spectrum.hpp SP_*
 LOAD = {"f32": "LoadF32", "f16": "LoadF16", "i16": "LoadI16"}
-MH = 16                                                            # kernels.hpp:951 halo cells per side
-RANGE_SINGLE, RANGE_SEQ, RANGE_PX = 0, 2, 3                        # dispatch.hpp:16 RangeKind
+MH = 16                                                            # cfar1d.hpp MH: halo cells per side
+RANGE_SINGLE, RANGE_SEQ, RANGE_PX = 0, 2, 3                        # dispatch.hpp RangeKind
 
 
 @dataclass(frozen=True)
@@ -94,55 +94,56 @@ class Cfg:
 
 # ---- validate() ---------------------------------------------------------------------------
 def illegal_reason(c: Cfg):
-    """plan.hip validate(), in its order; None when the configuration is legal."""
-    if c.n_range not in N_RANGE:                                   # :342
+    """plan.hip validate(), in its order (each arm cites the message validate fails with); None when the
+    configuration is legal."""
+    if c.n_range not in N_RANGE:                                   # "n_range=%u: must be a power of two in [64, 8192]"
         return "n_range"
-    if c.n_doppler not in N_DOPPLER:                               # :344
+    if c.n_doppler not in N_DOPPLER:                               # "n_doppler=%u: must be a power of two in [32, 1024]"
         return "n_doppler"
-    if not 1 <= c.n_rx <= 64:                                      # :346
+    if not 1 <= c.n_rx <= 64:                                      # "n_rx=%u: must be in [1, 64]"
         return "n_rx"
-    if c.window == "q15_rtl" and c.in_dtype != "i16":              # :351
+    if c.window == "q15_rtl" and c.in_dtype != "i16":              # "window Q15_RTL windows int16 ADC words: needs in_dtype I16"
         return "q15 needs i16"
-    if c.magnitude == "ambm" and c.n_rx != 1:                      # :355
+    if c.magnitude == "ambm" and c.n_rx != 1:                      # "mag_mode AMBM is defined for n_rx == 1 only"
         return "ambm needs n_rx 1"
-    if range_T(c.n_range) > c.n_doppler:                           # :361
+    if range_T(c.n_range) > c.n_doppler:                           # "n_doppler=%u smaller than the range kernel's chirp group"
         return "n_doppler below the chirp group"
     if c.cfar == "os1d":
         ref, guard, rank, alpha = c.cfar1d
-        if ref < 1 or rank >= 2 * ref:                             # :365
+        if ref < 1 or rank >= 2 * ref:                             # "1-D CFAR: need ref >= 1 and rank < 2*ref"
             return "rank"
-        if 2 * (ref + guard) + 1 > c.n_doppler:                    # :367
+        if 2 * (ref + guard) + 1 > c.n_doppler:                    # "1-D CFAR window wider than n_doppler"
             return "1-D window wider than n_doppler"
-        if not alpha > 0:                                          # :369
+        if not alpha > 0:                                          # "1-D CFAR alpha must be > 0"
             return "alpha"
-        if c.compat_cfar and not (alpha == int(alpha) and alpha <= 16384):   # :370
+        if c.compat_cfar and not (alpha == int(alpha) and alpha <= 16384):   # "compat CFAR: alpha is the integer SCALING_MULT (1..16384)"
             return "compat alpha"
     elif c.cfar == "os2d":
-        if c.cfar2d_rank_pct > 100:                                # :374
+        if c.cfar2d_rank_pct > 100:                                # "2-D CFAR: rank_pct %u > 100"
             return "2-D rank_pct"
-        if max(c.cfar2d) > 64:                                     # :375
+        if max(c.cfar2d) > 64:                                     # "2-D CFAR window extents out of range"
             return "2-D window extents"
         hr, _, hd, _, n_ref, _ = cfar2d_geom(c)
-        if not 1 <= n_ref <= 128:                                  # :379
+        if not 1 <= n_ref <= 128:                                  # "2-D CFAR: %d reference cells (supported 1..128)"
             return "2-D n_ref"
-        if 2 * hd + 1 > c.n_doppler:                               # :381
+        if 2 * hd + 1 > c.n_doppler:                               # "2-D CFAR window wider than n_doppler"
             return "2-D window wider than n_doppler"
-        if c.cfar2d_override > 7:                                  # :383
+        if c.cfar2d_override > 7:                                  # "scale_override is a 3-bit port (0..7)"
             return "2-D scale override"
-        if cfar2d_smem(c) > 160 * 1024:                            # :385
+        if cfar2d_smem(c) > 160 * 1024:                            # "2-D CFAR range extent too large for LDS"
             return "2-D range extent too large for LDS"
-    if c.compat_mti and c.mti == 0:                                # plan.hip:131
+    if c.compat_mti and c.mti == 0:                                # "compat MTI needs mti_mode 2 or 3"
         return "compat MTI needs MTI on"
-    if c.range_shift > 13:                                         # :394
+    if c.range_shift > 13:                                         # "range_shift=%u: must be in [0, 13]"
         return "range_shift"
     if c.spectrum == "s48":
-        if c.n_doppler < 64:                                       # :401
+        if c.n_doppler < 64:                                       # "spectrum_dtype S48 needs n_doppler >= 64"
             return "s48 needs n_doppler >= 64"
-        if c.mti != 0 or c.window == "q15_rtl":                    # :402
+        if c.mti != 0 or c.window == "q15_rtl":                    # "spectrum_dtype S48 is defined with MTI off and an fp32 window (not Q15_RTL)"
             return "s48 needs MTI off and an fp32 window"
-    if c.spectrum == "f16" and c.compat_mti:                       # plan.hip:144
+    if c.spectrum == "f16" and c.compat_mti:                       # "compat MTI is defined on the fp32 spectrum (spectrum_dtype F16)"
         return "compat MTI needs the fp32 spectrum"
-    if c.spectrum == "f16" and c.window == "q15_rtl":              # :409
+    if c.spectrum == "f16" and c.window == "q15_rtl":              # "window Q15_RTL is defined on the fp32 spectrum (spectrum_dtype F16)"
         return "q15 needs the fp32 spectrum"
     return None
 
@@ -153,29 +154,29 @@ def legal(c: Cfg) -> bool:
 
 # ---- K1 -----------------------------------------------------------------------------------
 def range_T(n: int) -> int:
-    """kernels.hpp:295 RangeGeom<N>::T (= SqGeom::T :488 and range_px's 2, inst_range.hip:66)."""
+    """range_kernels.hpp RangeGeom<N>::T (= SqGeom::T and the 2 of inst_range.hip range_px)."""
     return 16 if n <= 128 else 8 if n <= 512 else 4 if n == 1024 else 2
 
 
 @functools.lru_cache(maxsize=None)
 def range_select(n: int, in_dtype: str, window: str, spectrum: str):
-    """inst_range.hip range_info (:71-84) with want = kRangePx (the release library's preference,
+    """inst_range.hip range_info with want = kRangePx (the release library's preference,
     plan.hpp PlanPrefs::k1_want): (family, symbol, SP) or None where range_fn returns nullptr."""
     q15 = window == "q15_rtl"
     ld = LOAD[in_dtype]
-    if not q15 and spectrum in ("f32", "s48"):                     # :74
-        sp = 5 if spectrum == "s48" else 0                         # range_px :66 / range_sq :49
-        if n == 8192:                                              # :75, range_px_t :59
+    if not q15 and spectrum in ("f32", "s48"):                     # range_info: the pair kernels, `!q15 && (spec == FMCW_SPEC_F32 || spec == FMCW_SPEC_S48)`
+        sp = 5 if spectrum == "s48" else 0                         # inst_range.hip range_px / range_sq: SP_S48PS or SP_F32
+        if n == 8192:                                              # range_info `want >= kRangePx && n == 8192`, range_px_t
             return RANGE_PX, f"k_range_px<fmcw::{ld}, 4, {6 if sp == 5 else 4}, {sp}>", sp
-        if n == 4096:                                              # :76, SqPick<4096> :34
+        if n == 4096:                                              # range_info `want >= kRangeSeq && n == 4096`, SqPick<4096>
             return RANGE_SEQ, f"k_range_sq<4096, fmcw::{ld}, 16, 1, 3, {sp}>", sp
-    if spectrum == "s48":                                          # range_fn :20-26
+    if spectrum == "s48":                                          # range_fn: the S48 form by RangeGeom<N>::T
         if q15 or n > 2048:
             return None
         T = range_T(n)
         sp = 4 if T == 4 else 5 if T == 2 else 2
     else:
-        sp = 1 if spectrum == "f16" else 0                         # :27
+        sp = 1 if spectrum == "f16" else 0                         # range_fn: SP_F16 or SP_F32
     return RANGE_SINGLE, f"k_range<{n}, fmcw::{ld}, {'true' if q15 else 'false'}, {sp}>", sp
 
 
@@ -189,12 +190,12 @@ def k2_fast(c: Cfg) -> bool:
 
 
 def k2_prefetch(nc: int, mti: int) -> int:
-    """kernels.hpp:1443."""
+    """doppler_kernel.hpp k2_prefetch."""
     return 0 if mti else 16 if nc <= 256 else 8 if nc == 512 else 0
 
 
 def doppler_sp(c: Cfg) -> int:
-    """dispatch.hpp doppler_info (:43-45) and s48_form (:39)."""
+    """inst_doppler.hip doppler_info and dispatch.hpp s48_form."""
     if c.spectrum == "f16":
         return 1
     if c.spectrum == "s48":
@@ -204,7 +205,7 @@ def doppler_sp(c: Cfg) -> int:
 
 
 def cfar1d_branch(c: Cfg) -> str:
-    """kernels.hpp cfar1d_dispatch (:1346-1353)."""
+    """cfar1d.hpp cfar1d_dispatch."""
     ref, guard, rank, _ = c.cfar1d
     if c.compat_cfar:
         return "rtl"
@@ -220,7 +221,7 @@ def cfar1d_keys(c: Cfg, where: str) -> set:
     br = cfar1d_branch(c)
     keys = {f"cfar1d<{nc},{br}>/{where}"}
     if br == "runtime":
-        # kernels.hpp:1220-1221, :1251: offsets wrap with & (NC - 1); beyond the MH-cell halo only
+        # cfar1d.hpp cfar1d_wave<NC, 0, 0> (REF == 0 arms): offsets wrap with & (NC - 1); beyond the MH-cell halo only
         # this wrap keeps them inside the row, and at 2 (ref + guard) + 1 = NC - 1 the two sides meet
         if ref + guard > MH:
             keys.add(f"cfar1d<{nc},runtime>/window>halo/{where}")
@@ -233,96 +234,96 @@ def cfar2d_geom(c: Cfg):
     """plan.hip cfar2_args: (hr, gr, hd, gd, n_ref, rank)."""
     rr, gr, rd, gd = c.cfar2d
     hr, hd = rr + gr, rd + gd
-    n_ref = (2 * hr + 1) * (2 * hd + 1) - (2 * gr + 1) * (2 * gd + 1)        # :318
-    rank = min(n_ref * c.cfar2d_rank_pct // 100, n_ref - 1)                   # :320
+    n_ref = (2 * hr + 1) * (2 * hd + 1) - (2 * gr + 1) * (2 * gd + 1)        # cfar2_args a.n_ref
+    rank = min(n_ref * c.cfar2d_rank_pct // 100, n_ref - 1)                   # cfar2_args a.rank
     return hr, gr, hd, gd, n_ref, rank
 
 
 def cfar2d_TR(nc: int) -> int:
-    """cfar2d.hpp Cfar2DGeom<NC>::TR (:106): CUT rows of a workgroup step, WPB 4 x WR = 1024 / NC."""
+    """cfar2d.hpp Cfar2DGeom<NC>::TR: CUT rows of a workgroup step, WPB 4 x WR = 1024 / NC."""
     return 4096 // nc
 
 
 def cfar2d_lv(c: Cfg) -> bool:
-    """inst_cfar2.hip lv_window (:15)."""
+    """inst_cfar2.hip lv_window."""
     hr, gr, hd, gd, _, _ = cfar2d_geom(c)
     return (hd, gd, hr, gr) == (6, 2, 5, 1)
 
 
 def cfar2d_smem(c: Cfg) -> int:
-    """The LDS bytes of the K3a kernel cfar2_info picks (inst_cfar2.hip info_t :20-35)."""
+    """The LDS bytes of the K3a kernel cfar2_info picks (inst_cfar2.hip info_t)."""
     nc = c.n_doppler
     hr = cfar2d_geom(c)[0]
     if cfar2d_lv(c):
-        if nc == 1024:      # cfar2d.hpp LvGeom::SMEM (:849-858), HR 5: NR x ROWB + (HIST + CAPB + 2 CAPT) x 4
+        if nc == 1024:      # cfar2d.hpp LvGeom::SMEM, HR 5: NR x ROWB + (HIST + CAPB + 2 CAPT) x 4
             return (cfar2d_TR(nc) + 2 * 5 + 1) * (2 * (nc + 16) + nc // 2) + (144 + 192 + 2 * 64) * 4
         hr = 5
-    # cfar2d.hpp cfar2d_smem_bytes (:131-135): (TR + 2 hr) x (RB + 2 KRS) + kCfar2dList x 4
+    # cfar2d.hpp cfar2d_smem_bytes: (TR + 2 hr) x (RB + 2 KRS) + kCfar2dList x 4
     return (cfar2d_TR(nc) + 2 * hr) * ((nc + 2 * MH + 16) + 2 * (nc + 2 * MH)) + (2 * 256 + 16) * 4
 
 
 def cfar2d_strips(n_range: int, nc: int, steps: int):
-    """launch.hip launch_cfar (tpf, n_strips) and the strip loop of k_cfar2d (cfar2d.hpp:543-557;
-    k_cfar2d_lv :1145-1162): [(strip index within the frame, its steps)] for a strip length."""
+    """launch.hip launch_cfar (tpf, n_strips) and the strip loop of k_cfar2d (cfar2d.hpp `t_beg`, `t_end`;
+    k_cfar2d_lv the same): [(strip index within the frame, its steps)] for a strip length."""
     tpf = -(-n_range // cfar2d_TR(nc))                # workgroup steps per frame
     s = min(steps, tpf)
     return [(i, min(s, tpf - i * s)) for i in range(-(-tpf // s))]
 
 
 def cfar2d_select(c: Cfg, steps: int = 0):
-    """inst_cfar2.hip cfar2_info (:15-46): [(key, symbol)], then (key, None) for every branch of
+    """inst_cfar2.hip cfar2_info: [(key, symbol)], then (key, None) for every branch of
     cfar2d.hpp the configuration, the shape and the strip length `steps` (0: the cost model's
     choice, which depends on the CU count and is not mirrored) take, tagged with its kernel."""
     nc = c.n_doppler
     hr, gr, hd, gd, n_ref, rank = cfar2d_geom(c)
-    lv = cfar2d_lv(c)                                              # lv_window :15
-    rules = lv and nc == 1024                                      # rules_kernel :17 (static_assert :26)
+    lv = cfar2d_lv(c)                                              # inst_cfar2.hip lv_window
+    rules = lv and nc == 1024                                      # rules_kernel (info_t static_assert N == 1024)
     if rules:
         a = f"k_cfar2d_lv<1024, 5, 1, {'true' if c.compat_cfar else 'false'}>"
     elif lv:
-        a = f"k_cfar2d<{nc}, 6, 2, 5, 1>"                          # :31
+        a = f"k_cfar2d<{nc}, 6, 2, 5, 1>"                          # info_t, lv without rules_kernel: k_cfar2d<N, 6, 2, 5, 1>
     else:
-        a = f"k_cfar2d<{nc}, 0, 0, 0, 0>"                          # :21
+        a = f"k_cfar2d<{nc}, 0, 0, 0, 0>"                          # info_t default: k_cfar2d<N, 0, 0>
     out = [(s.replace(" ", ""), s) for s in (a, f"k_cfar2d_decide<{nc}>", f"k_cfar2d_emit<{nc}>")]
     ka, kb, kc = (k for k, _ in out)
     keys = []
     if c.compat_cfar:
         if not rules:                # k_cfar2d_lv carries compat in its symbol (CMP)
-            keys.append(f"{ka}/compat")                            # cfar2d.hpp:517, :674, :750 (q17 cells)
-        keys.append(f"{kb}/compat")                                # :1469 (CMP: integer mean and brackets :1440)
-        keys.append(f"{kc}/compat")                                # :1535
+            keys.append(f"{ka}/compat")                            # cfar2d.hpp k_cfar2d `a.compat ? q17... : nonneg...` (q17 cells)
+        keys.append(f"{kb}/compat")                                # k_cfar2d_decide `a.compat` (cfar2d_decide_run CMP: integer mean and brackets)
+        keys.append(f"{kc}/compat")                                # k_cfar2d_emit `dd.mag = a.compat ? q17(v) : nonneg(v)`
     if c.cfar2d_override:
-        keys.append(f"{ka}/override")                              # :340, :378 (k_cfar2d); :1224 (k_cfar2d_lv)
-        keys.append(f"{kb}/override")                              # :1437-1438: no mean, no bracket
-    elif not c.compat_cfar:                                        # fl(sum / n) :1399-1401, :1447
+        keys.append(f"{ka}/override")                              # `a.override_` in cfar2d_exact_a (k_cfar2d) and `s2ok` (k_cfar2d_lv)
+        keys.append(f"{kb}/override")                              # cfar2d_decide_run `if (!a.override_)`: no mean, no bracket
+    elif not c.compat_cfar:                                        # cfar2d_decide_run fl(sum / n): `inv_n`, `n_pow2`
         keys.append(f"{kb}/n_ref={'pow2' if n_ref & (n_ref - 1) == 0 else 'div'}")
     if n_ref <= 64:
-        keys.append(f"{kb}/n_ref<=64")                             # okb :1396 is never true
-    if rank == 0:                                                  # need = n_ref :498, :1090; select k = 0 :1458
+        keys.append(f"{kb}/n_ref<=64")                             # cfar2d_decide_run `okb` is never true
+    if rank == 0:                                                  # `need = a.n_ref - a.rank` (k_cfar2d, k_cfar2d_lv); wave_select_kth k = 0
         keys += [f"{ka}/rank=0", f"{kb}/rank=0"]
     if rank == n_ref - 1:                                          # need = 1; select k = n_ref - 1
         keys += [f"{ka}/rank=n_ref-1", f"{kb}/rank=n_ref-1"]
     if not lv:                       # runtime geometry of k_cfar2d<NC,0,0,0,0>
-        if hd > MH:                                                # :308, :358 wrap with & (NC - 1)
+        if hd > MH:                                                # cfar2d_screen7_generic `pm`, cfar2d_exact_a: wrap with & (NC - 1)
             keys.append(f"{ka}/window>halo")
         if 2 * hd + 1 == nc - 1:                                   # the two Doppler sides meet at the wrap
             keys.append(f"{ka}/maximal")
-        if hr == 0:                                                # nr == TR :503, every row tested :704
+        if hr == 0:                                                # k_cfar2d `nr = TR + 2 * a.hr` == TR, every row `tested`
             keys.append(f"{ka}/hr=0")
-        if hd == 0:                                                # nps == 0 :302, :314: the screen counts nothing
+        if hd == 0:                                                # cfar2d_screen7_generic `nps` == 0: the screen counts nothing
             keys.append(f"{ka}/hd=0")
-        if hr >= cfar2d_TR(nc):                                    # the ring turn :663 moves fewer rows than a halo
+        if hr >= cfar2d_TR(nc):                                    # the ring turn (k_cfar2d `rr.base +=`) moves fewer rows than a halo
             keys.append(f"{ka}/hr>=TR")
-    if c.n_range < cfar2d_TR(nc):                                  # n_wt < WPB :559, has_tile :694
+    if c.n_range < cfar2d_TR(nc):                                  # k_cfar2d `n_wt` < WPB, `has_tile`
         keys.append(f"{ka}/step=partial")
     if steps:
         strips = cfar2d_strips(c.n_range, nc, steps)
         for i, n in strips:
-            if n == 1:                                             # first == last :557: no turn, no prefetch
+            if n == 1:                                             # k_cfar2d `first` == `last`: no turn, no prefetch
                 keys.append(f"{ka}/strip=one-step")
-            else:                                                  # up :554 (kK3AltDir): the turn :663, prefetch :679
+            else:                                                  # k_cfar2d `up` (kK3AltDir): the ring turn `rr.base +=`, the prefetch `if (!last)`
                 keys.append(f"{ka}/strip={'up' if i & 1 else 'down'}")
-        if strips[-1][1] < strips[0][1]:                           # t_end = min(t_beg + steps, wg_per_frame) :543
+        if strips[-1][1] < strips[0][1]:                           # k_cfar2d `t_end = min(t_beg + steps, wg_per_frame)`
             keys.append(f"{ka}/strip=short-last")
     return out + [(k, None) for k in keys]
 
@@ -338,7 +339,7 @@ def select(c: Cfg, api: str = "process", steps: int = 0):
         _, sym, sp = range_select(c.n_range, c.in_dtype, c.window, "f32")
         return [(sym.replace("fmcw::", "").replace(" ", "") + "/cw=0", sym)]
     if api == "cfar":
-        if c.cfar == "os1d":                                       # launch_cfar :611-618
+        if c.cfar == "os1d":                                       # launch.hip launch_cfar
             out.append((f"k_cfar1d<{nc}>", f"k_cfar1d<{nc}>"))
             out += [(k, None) for k in cfar1d_keys(c, "stage")]
         elif c.cfar == "os2d":
@@ -349,51 +350,51 @@ def select(c: Cfg, api: str = "process", steps: int = 0):
     if sel is None:
         return []
     _, sym, _ = sel
-    cw = int(c.mti == 0 and c.window != "q15_rtl")                  # chirp_w :969
+    cw = int(c.mti == 0 and c.window != "q15_rtl")                  # fmcw_api.hip `chirp_w = c.mti_mode == FMCW_MTI_OFF && !p.q15 ? h->win_d : nullptr`
     out.append((sym.replace("fmcw::", "").replace(" ", "") + f"/cw={cw}", sym))
     fast = k2_fast(c)
     sp = doppler_sp(c)
-    if sp >= 2 and (nc < 64 or c.mti != 0):                        # inst_doppler_s48.hip dfn_t :11-16
+    if sp >= 2 and (nc < 64 or c.mti != 0):                        # inst_doppler_s48.hip dfn_t
         return []
     T = range_T(c.n_range)
-    P = nc // 16                                                   # DopplerGeom::P kernels.hpp:997
-    WR, WPB = 64 // P, 4                                           # :998, :1001
+    P = nc // 16                                                   # cfar1d.hpp DopplerGeom::P
+    WR, WPB = 64 // P, 4                                           # DopplerGeom::WR, ::WPB
     npf = k2_prefetch(nc, c.mti)
     if npf == 0:
         addr = ""
     elif sp in (4, 5):
-        addr = "/strided"                                          # kernels.hpp:1556
+        addr = "/strided"                                          # doppler_kernel.hpp k_doppler prefetch, the strided-S48 arm
     elif P & (T - 1) == 0:
-        addr = "/uniform"                                          # :1569
+        addr = "/uniform"                                          # k_doppler prefetch `(P & (T - 1)) == 0`: the uniform arm
     else:
-        addr = "/per-point"                                        # :1602
+        addr = "/per-point"                                        # k_doppler prefetch, the last arm: an address per point
     kind = "FAST" if fast else "GEN"
     out.append((f"k_doppler<{nc},mti={c.mti},{SP_NAME[sp]},{kind}>/pf={npf}{addr}",
                 f"k_doppler<{nc}, {c.mti}, {sp}, {'true' if fast else 'false'}>"))
     nbytes = 6 if sp >= 2 else 8
-    if WPB * WR * nbytes * T < 128:                                # xcd :1623
+    if WPB * WR * nbytes * T < 128:                                # k_doppler `xcd`
         out.append((f"k_doppler/xcd-remap<NC={nc},B={nbytes},T={T}>", None))
     tiles = c.n_range // WR
-    out.append((f"k_doppler<{nc}>/tile-order={'grouped' if tiles % WPB == 0 else 'frame-minor'}", None))   # grp :1525
-    if c.n_rx > 1:                                                 # the rx loop :1644, prefetch across rx :1724
+    out.append((f"k_doppler<{nc}>/tile-order={'grouped' if tiles % WPB == 0 else 'frame-minor'}", None))   # k_doppler `grp`
+    if c.n_rx > 1:                                                 # k_doppler: the rx loop, the prefetch site `same ? rx + 1 : 0`
         out.append((f"k_doppler/nci<pf={npf},{SP_NAME[sp]}>", None))
         if c.n_rx % 2:
             out.append(("k_doppler/nci/odd-nrx", None))
     if not fast:                                                   # runtime branches of the generic kernel
         if c.magnitude == "ambm":
-            out.append((f"k_doppler<{nc},{SP_NAME[sp]},GEN>/ambm", None))        # :1729, :1747
+            out.append((f"k_doppler<{nc},{SP_NAME[sp]},GEN>/ambm", None))        # k_doppler `mag_mode == FMCW_MAG_AMBM`, `ambm`
         if c.map_kind == "db":
-            out.append((f"k_doppler<{nc},{SP_NAME[sp]},GEN>/db", None))          # :1775
+            out.append((f"k_doppler<{nc},{SP_NAME[sp]},GEN>/db", None))          # k_doppler `!FAST && db_map`
         if c.window == "q15_rtl":
-            out.append((f"k_doppler<{nc},{SP_NAME[sp]},GEN>/q15d", None))        # :1502, :1707
+            out.append((f"k_doppler<{nc},{SP_NAME[sp]},GEN>/q15d", None))        # k_doppler `q15d`: the wv_d load, win_q15c
         if c.mti and (c.compat_mti or c.window == "q15_rtl"):
             # the canceller on 16-bit words: neighbours re-read and re-quantised, saturating output
-            out.append((f"k_doppler<{nc},mti={c.mti},{SP_NAME[sp]},GEN>/words", None))        # :1692-1704
-            if c.window == "q15_rtl":        # the integer window on the canceller's output, :1707 after :1704
+            out.append((f"k_doppler<{nc},mti={c.mti},{SP_NAME[sp]},GEN>/words", None))        # k_doppler `words`: q16c_count .. sat16c_count
+            if c.window == "q15_rtl":        # the integer window on the canceller's output: win_q15c after sat16c_count
                 out.append((f"k_doppler<{nc},mti={c.mti},{SP_NAME[sp]},GEN>/words+q15d", None))
-    if c.cfar == "os1d":                                           # :1784-1787
+    if c.cfar == "os1d":                                           # k_doppler `cf.enabled`: cfar1d_wave<NC, 8, 2, true> / cfar1d_dispatch
         out += [(k, None) for k in cfar1d_keys(c, "fused-fast" if fast else "fused-generic")]
-    elif c.cfar == "os2d":                                         # launch_cfar from fmcw_enqueue :989-999
+    elif c.cfar == "os2d":                                         # launch.hip launch_cfar from fmcw_enqueue
         out += cfar2d_select(c)
     return out
 
@@ -403,14 +404,15 @@ def variants(c: Cfg, api: str = "process", steps: int = 0) -> set:
 
 
 def range_family(c: Cfg, api: str = "process") -> int:
-    """FMCW_INFO_RANGE_KERNEL: the family fmcw_create picked with the handle's spectrum (:758)."""
+    """FMCW_INFO_RANGE_KERNEL: the family fmcw_create picked with the handle's spectrum (fmcw_api.hip fmcw_create)."""
     return range_select(c.n_range, c.in_dtype, c.window, c.spectrum)[0]
 
 
 # ---- the persistent loops ------------------------------------------------------------------
 # K1, K2, k_cfar1d and K3a stride over their units with `for (g = blockIdx.x; g < n; g += gridDim.x)`
-# (kernels.hpp:373, :549, :710, :1370, :1627; cfar2d.hpp:539, :1143); K3b / K3c over candidates and
-# wave tiles per wave (cfar2d.hpp:1403, :1484).  The grids are occupancy x CUs (launch.hip
+# (the `g += gridDim.x` loops of k_range, k_range_sq, k_range_px, the `tile +=` loops of k_cfar1d, k_doppler and
+# the strip loops of k_cfar2d, k_cfar2d_lv); K3b / K3c over candidates and wave tiles per wave (cfar2d.hpp
+# cfar2d_decide_run, k_cfar2d_emit `nw`).  The grids are occupancy x CUs (launch.hip
 # device_grids; 1024 for K3b / K3c), so at the shapes of this table a workgroup runs one iteration
 # unless the grid is capped (fmcw_set_param FMCW_PARAM_GRID_*, Case.grid).  A key "<key>/loop" says: a
 # case ran that kernel so that its busiest workgroup went through the loop at least LOOP_MIN times.
@@ -422,8 +424,8 @@ MAX_CELLS = 2048 * 1024      # no case is larger than the "fast-xcd" shape: 2048
 
 def loopable(key: str, sym) -> bool:
     """Keys that get a "/loop" twin: those that carry a kernel symbol, and K2's NCI, XCD-remap and
-    tile-order keys (the rx loop carries the prefetch into the next tile :1724; xcd_block_id :1432
-    and tile_fl :1526 decide which units a workgroup strides over)."""
+    tile-order keys (the rx loop carries the prefetch into the next tile at k_doppler's prefetch site;
+    xcd_block_id and tile_fl decide which units a workgroup strides over)."""
     return sym is not None or key.startswith(("k_doppler/nci<", "k_doppler/xcd-remap<")) or "/tile-order=" in key
 
 
@@ -438,35 +440,35 @@ def loop_kernel(key: str) -> str:
 
 
 def tiles_frame(c: Cfg) -> int:
-    """Wave tiles of a frame: n_range / WR, WR = 64 / P rows of P = NC / 16 lanes (kernels.hpp:997-998;
+    """Wave tiles of a frame: n_range / WR, WR = 64 / P rows of P = NC / 16 lanes (cfar1d.hpp DopplerGeom::P, ::WR;
     plan.hip tiles_frame)."""
     return c.n_range // (64 // (c.n_doppler // 16))
 
 
 def k1_units(c: Cfg, nf: int) -> int:
-    """launch.hip:73: n_groups = nf * n_rx * (n_doppler / T) chirp groups per K1 launch."""
+    """launch.hip launch_range: n_groups = nf * n_rx * (n_doppler / T) chirp groups per K1 launch."""
     return nf * c.n_rx * (c.n_doppler // range_T(c.n_range))
 
 
 def tile_units(c: Cfg, nf: int) -> int:
-    """launch.hip:48-50 (K2 and k_cfar1d): ceil(nf * tiles_frame / WPB) workgroup steps, WPB = 4."""
+    """launch.hip tile_grid (K2 and k_cfar1d): ceil(nf * tiles_frame / WPB) workgroup steps, WPB = 4."""
     return -(-nf * tiles_frame(c) // 4)
 
 
 def k3a_units(c: Cfg, nf: int, steps: int) -> int:
-    """launch.hip:110-113: nf * ceil(tpf / steps) strips, tpf = ceil(tiles_frame / 4)."""
+    """launch.hip launch_cfar `n_strips`: nf * ceil(tpf / steps) strips, tpf = ceil(tiles_frame / 4)."""
     return nf * len(cfar2d_strips(c.n_range, c.n_doppler, steps))
 
 
 def k3c_units(c: Cfg, nf: int) -> int:
-    """Wave tiles of a K3 launch (at most: k_cfar2d_emit takes those with candidates, cfar2d.hpp:1483),
+    """Wave tiles of a K3 launch (at most: k_cfar2d_emit takes those with candidates, cfar2d.hpp `cands.ctr[1]`),
     shared by the 4 waves of each workgroup."""
     return nf * tiles_frame(c)
 
 
 def wg_units(units: int, grid: int):
     """The units each workgroup of a launch takes, in its order: the launch sites bound the grid by
-    the unit count (launch.hip:50, :78, :114), workgroup b takes b, b + grid, ..."""
+    the unit count (launch.hip tile_grid, launch_range, launch_cfar), workgroup b takes b, b + grid, ..."""
     g = min(units, grid)
     return [list(range(b, units, g)) for b in range(g)]
 
@@ -478,7 +480,7 @@ def busiest(units: int, grid: int) -> int:
 
 def k3a_walk(c: Cfg, nf: int, steps: int, grid: int):
     """Per workgroup, the strips it takes as (frame, "down" / "up" / "one-step"): strip g is strip
-    g / nf of frame g % nf, odd strips walk upwards (cfar2d.hpp:542-557, :1144-1162)."""
+    g / nf of frame g % nf, odd strips walk upwards (cfar2d.hpp k_cfar2d / k_cfar2d_lv strip loop)."""
     per_frame = cfar2d_strips(c.n_range, c.n_doppler, steps)
     out = []
     for mine in wg_units(nf * len(per_frame), grid):
@@ -503,7 +505,7 @@ def k3a_turns(walk) -> bool:
 
 
 def launch_frames(nf: int, chunk_frames: int):
-    """Frames of each K1 / K2 launch of one fmcw_process call (fmcw_api.hip:288-292); the auto chunk
+    """Frames of each K1 / K2 launch of one fmcw_process call (fmcw_api.hip, the `f0 += p.chunk` loop); the auto chunk
     holds every case of this table whole."""
     ch = chunk_frames or nf
     return [min(ch, nf - f0) for f0 in range(0, nf, ch)]
@@ -585,7 +587,7 @@ def reachable_with_symbols():
                 if illegal_reason(c):
                     continue
                 sel = select(c, "process")
-                if not sel:                   # fmcw_create: "no kernel for this configuration" (:770)
+                if not sel:                   # plan.hip build_plan: "no kernel for this configuration"
                     continue
                 found.update(sel)
                 found.update(select(c, "range_ct"))
@@ -1232,7 +1234,7 @@ def cfar2d_source_constants():
 def cfar2d_dense(c: Cfg) -> bool:
     """rank 0: the threshold is scale x the smallest reference, nearly every tested cell detects.
     These cases run with det_capacity set (test_gpu_matrix), where a wave tile's slot holds 1/32 of
-    its cells and denser tiles move to the sink's overflow region (kernels.hpp det_reserve_wave);
+    its cells and denser tiles move to the sink's overflow region (det_sink.hpp det_reserve_wave);
     with det_capacity 0, as every other case runs, a slot holds the whole tile."""
     return c.cfar == "os2d" and cfar2d_geom(c)[5] == 0
 
@@ -1243,7 +1245,7 @@ def cfar2d_map(case: Case):
 
 
 def cfar2d_clamped(m):
-    """fmcw_cfar takes negative cells and -0.0 as +0 (kernels.hpp nonneg); the references see that map."""
+    """fmcw_cfar takes negative cells and -0.0 as +0 (det_sink.hpp nonneg); the references see that map."""
     return np.where(m > 0, m, np.float32(0.0)).astype(np.float32)
 
 
@@ -1329,7 +1331,7 @@ SUB16 = 2.0 ** -25        # half the spacing of fp16 subnormals: the absolute ro
 
 def fp16_row_error(case: Case):
     """E[frame][range]: how far the fp16 spectrum (fmcw.h FMCW_SPEC_F16: half2(X / N_range) between
-    K1 and K2, kernels.hpp:266 rounds to nearest) can move any cell of a range row of the map, from
+    K1 and K2, spectrum.hpp pack_h2 rounds to nearest) can move any cell of a range row of the map, from
     the format alone.  A stored point p has |dp| <= U16 |p| + sqrt(2) SUB16 (relative rounding, or
     the subnormal spacing); the canceller sums 2 (4) points' errors; the Doppler FFT output of the
     row moves by at most sum_c w[c] |d[c]|; |.| is 1-Lipschitz, NCI takes the 2-norm over rx, and

@@ -83,7 +83,7 @@ def test_gfx950_code_object_present(lib_built, tmp_path):
 def test_no_wide_store_data_hazard(lib_built, tmp_path):
     """No VALU write of a dwordx3/x4 store's data VGPRs within 2 wait states of the store in any
     shipped kernel (tools/store_hazard_scan.py; hipcc leaves that hazard unpadded for stores with
-    an SGPR soffset, which corrupted S48 tiles intermittently before kernels.hpp store_b96_padded)."""
+    an SGPR soffset, which corrupted S48 tiles intermittently before spectrum.hpp store_b96_padded)."""
     _, cos = extract_code_objects(tmp_path)
     if not cos:
         pytest.skip("this llvm-objdump cannot extract offload bundles")

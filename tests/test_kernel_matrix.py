@@ -161,7 +161,7 @@ def test_loop_case_runs_its_loops(case):
     """Every "/loop" key a case claims, recomputed here from the unit counts of the launch sites and
     the loops as the kernels write them: the busiest workgroup runs at least 3 iterations in every
     launch of the call, and its last has no next unit.  K2 per wave (tile = bid WPB + wave, step grid
-    WPB, kernels.hpp:1627), with the XCD remap a permutation that is not the identity; K3a with a down
+    WPB, doppler_kernel.hpp k_doppler tile loop), with the XCD remap a permutation that is not the identity; K3a with a down
     strip right after an up strip and an up strip right after a down strip in one workgroup (strips of
     one step: two frames in a row); K3c per wave of the 4 grid waves.  A case with a grid claims at
     least one such key."""
@@ -170,23 +170,23 @@ def test_loop_case_runs_its_loops(case):
     assert claimed, "a capped grid that loops nowhere"
     assert all(k in case.keys() for k in claimed)
     kernels = {K.loop_kernel(k) for k in claimed}
-    T = 16 if c.n_range <= 128 else 8 if c.n_range <= 512 else 4 if c.n_range == 1024 else 2    # kernels.hpp:295
-    wr = 64 // (c.n_doppler // 16)                                                                # :997-998
+    T = 16 if c.n_range <= 128 else 8 if c.n_range <= 512 else 4 if c.n_range == 1024 else 2    # range_kernels.hpp RangeGeom<N>::T
+    wr = 64 // (c.n_doppler // 16)                                                                # cfar1d.hpp DopplerGeom::WR
     per_launch = K.launch_frames(case.nf, case.chunk_frames) if case.group in ("process", "cfar1d") else [case.nf]
     assert sum(per_launch) == case.nf and (not case.chunk_frames or max(per_launch) == case.chunk_frames < case.nf)
     if "k1" in kernels:
         for n in per_launch:
-            walks = _stride(n * c.n_rx * c.n_doppler // T, G)                                   # launch.hip:73
+            walks = _stride(n * c.n_rx * c.n_doppler // T, G)                                   # launch.hip launch_range n_groups
             assert max(map(len, walks)) >= 3
             assert all(w[-1] + len(walks) >= n * c.n_rx * c.n_doppler // T for w in walks)
     if kernels & {"k2", "xcd", "cfar1d"}:
         for n in per_launch:
-            n_tiles = n * (c.n_range // wr)                                                      # launch.hip:49
-            grid = min(-(-n_tiles // 4), G)                                                      # :50
+            n_tiles = n * (c.n_range // wr)                                                      # launch.hip tile_grid
+            grid = min(-(-n_tiles // 4), G)                                                      # tile_grid: min(ceil(n_tiles / wpb), grid.doppler)
             per_wave = []
             for b in range(grid):
                 remap = "xcd" in kernels and grid % 8 == 0
-                bid = (b & 7) * (grid >> 3) + (b >> 3) if remap else b                           # kernels.hpp:1432-1435
+                bid = (b & 7) * (grid >> 3) + (b >> 3) if remap else b                           # doppler_kernel.hpp xcd_block_id
                 per_wave += [list(range(bid * 4 + wv, n_tiles, grid * 4)) for wv in range(4)]
             assert sorted(t for w in per_wave for t in w) == list(range(n_tiles))               # every tile once
             assert max(map(len, per_wave)) >= 3
@@ -196,20 +196,20 @@ def test_loop_case_runs_its_loops(case):
                 assert [(b & 7) * (grid >> 3) + (b >> 3) for b in range(grid)] != list(range(grid))
     if kernels & {"k3a", "k3b", "k3c"}:
         assert case.group == "cfar2d" and case.steps
-        tr = 4 * wr                                                                              # cfar2d.hpp:106
-        tpf = -(-c.n_range // tr)                                                                # launch.hip:110
+        tr = 4 * wr                                                                              # cfar2d.hpp Cfar2DGeom::TR
+        tpf = -(-c.n_range // tr)                                                                # launch.hip launch_cfar tpf
         steps = min(case.steps, tpf)
         spf = -(-tpf // steps)
-        walks = _stride(case.nf * spf, G)                                                        # launch.hip:113-114
+        walks = _stride(case.nf * spf, G)                                                        # launch.hip launch_cfar n_strips, grid
         if "k3a" in kernels:
             assert max(map(len, walks)) >= 3
             ok = False
             for w in walks:
                 seq = []
                 for g in w:
-                    f, i = g % case.nf, g // case.nf                                             # cfar2d.hpp:542-543
+                    f, i = g % case.nf, g // case.nf                                             # cfar2d.hpp k_cfar2d strip loop
                     n_steps = min(i * steps + steps, tpf) - i * steps
-                    seq.append((f, None if n_steps == 1 else bool(i & 1)))                       # :554, :557
+                    seq.append((f, None if n_steps == 1 else bool(i & 1)))                       # k_cfar2d `up`, `first` / `last`
                 pairs = list(zip(seq, seq[1:]))
                 if all(d is None for _, d in seq):
                     ok |= any(a[0] != b[0] for a, b in pairs)
@@ -224,7 +224,7 @@ def test_loop_case_runs_its_loops(case):
 @pytest.mark.parametrize("case", [c for c in LOOPS if c.group == "cfar2d"], ids=lambda c: c.id)
 def test_cfar2d_loop_case_has_candidates(case):
     """K3b strides over the candidates, 4 waves per workgroup and one candidate per wave at a time
-    (cfar2d.hpp:1403-1428); their number depends on the data, and every detection was a candidate.
+    (cfar2d.hpp cfar2d_decide_run); their number depends on the data, and every detection was a candidate.
     The oracle's detections on the case's map, all in one launch (3 frames), are at least 3 per wave
     of the capped grid."""
     dets, _, _ = _oracle2d(case)

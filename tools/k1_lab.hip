@@ -18,7 +18,7 @@
 #include <string>
 #include <vector>
 
-#include "../fpga-fmcw-radar-processor_amd/csrc/kernels.hpp"
+#include "../fpga-fmcw-radar-processor_amd/csrc/range_kernels.hpp"
 
 using namespace fmcw;
 

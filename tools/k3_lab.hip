@@ -23,7 +23,7 @@
 
 #include <functional>
 
-#include "../fpga-fmcw-radar-processor_amd/csrc/kernels.hpp"
+#include "../fpga-fmcw-radar-processor_amd/csrc/cfar2d.hpp"
 #include "../fpga-fmcw-radar-processor_amd/csrc/plan.hpp"  // cfar2_steps_model
 #ifdef K3_LAB_PREV  // the previous K3 (tools/cfar2d_prev.hpp, e.g. git show HEAD~:.../cfar2d.hpp) for A/B
 namespace fmcw {
