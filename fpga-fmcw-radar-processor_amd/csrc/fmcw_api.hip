@@ -38,13 +38,9 @@ int check_launch(const char* what) {
   return FMCW_OK;
 }
 
-}  // namespace fmcw
-
-namespace {
-
 // fp32 window table: Hamming with the RTL's half-ROM mirrored address, computed in fp64
 // (window_multiplier.vhd:34-49, :97-102).  WIN_NONE uploads ones.
-std::vector<float> window_table(uint32_t n, int kind, uint32_t shift = 0) {
+std::vector<float> window_table(uint32_t n, int kind, uint32_t shift) {
   std::vector<float> w(n, std::ldexp(1.0f, -(int)shift));  // 2^-shift: exact
   if (kind != FMCW_WIN_Q15_RTL && kind != FMCW_WIN_HAMMING) return w;
   const uint32_t half = n / 2;
@@ -58,6 +54,10 @@ std::vector<float> window_table(uint32_t n, int kind, uint32_t shift = 0) {
   }
   return w;
 }
+
+}  // namespace fmcw
+
+namespace {
 
 // The A/B knobs of FMCW_LAB builds (tools/build_variants.sh), read from the environment once per
 // fmcw_create, after the release plan and grids exist; the release library reads no environment.

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <vector>
+
 #include "../../include/fmcw.h"
 
 namespace fmcw {
@@ -11,6 +13,9 @@ namespace fmcw {
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 // FMCW_OK, or FMCW_EHIP with the pending launch error of kernel `what`
 int check_launch(const char* what);
+// The fp32 window table of n points the kernels multiply by (fmcw_api.hip): FMCW_WIN_HAMMING, or
+// ones for FMCW_WIN_NONE, scaled by 2^-shift; FMCW_WIN_Q15_RTL gives the ROM integers.
+std::vector<float> window_table(uint32_t n, int kind, uint32_t shift = 0);
 
 }  // namespace fmcw
 

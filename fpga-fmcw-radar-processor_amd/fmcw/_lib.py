@@ -41,6 +41,8 @@ GRID_KEYS = {"grid_range": (PARAM_GRID_RANGE, INFO_GRID_RANGE), "grid_doppler": 
 RANGE_KERNELS = ("k_range", "k_range2 (retired)", "k_range_sq", "k_range_px")
 STATUS_WORDS = 4      # FMCW_STATUS_WORDS: n_dets_dev = found, lost, window / word saturations
 PLOT_STATUS_WORDS = 2  # FMCW_PLOT_STATUS_WORDS: n_plots_dev = plots found, records not examined
+BEARING_STATUS_WORDS = 2  # FMCW_BEARING_STATUS_WORDS: n_out_dev = records processed, out of range
+BEARING_NO_ANGLE, BEARING_ONE_RX, BEARING_OUT_OF_RANGE = 1, 2, 4   # fmcw_bearing.flags bits
 
 STATUS_NAMES = {0: "FMCW_OK", -1: "FMCW_EINVAL", -2: "FMCW_ENOMEM", -3: "FMCW_EHIP",
                 -4: "FMCW_EDETCAP", -5: "FMCW_ENODEV"}
@@ -78,6 +80,18 @@ class FmcwPlot(C.Structure):
 class FmcwPlotsConfig(C.Structure):
     _fields_ = [("n_range", C.c_uint32), ("n_doppler", C.c_uint32), ("win_range", C.c_uint32),
                 ("win_doppler", C.c_uint32), ("max_dets", C.c_uint32), ("device_id", C.c_int32)]
+
+
+class FmcwBearing(C.Structure):
+    _fields_ = [("frame", C.c_uint32), ("range", C.c_uint16), ("doppler", C.c_uint16),
+                ("flags", C.c_uint32), ("nu", C.c_float), ("sin_theta", C.c_float),
+                ("power", C.c_float), ("coherence", C.c_float), ("reserved", C.c_uint32)]
+
+
+class FmcwBearingsConfig(C.Structure):
+    _fields_ = [("n_range", C.c_uint32), ("n_doppler", C.c_uint32), ("n_rx", C.c_uint32),
+                ("window", C.c_int32), ("mti_mode", C.c_int32), ("spacing", C.c_float),
+                ("max_records", C.c_uint32), ("device_id", C.c_int32)]
 
 
 class FmcwTwsConfig(C.Structure):
@@ -129,6 +143,11 @@ SIGNATURES = {
     "fmcw_plots_destroy": (_I, [_VP]),
     "fmcw_plots_enqueue": (_I, [_VP, _VP, _SZ, _VP, _VP, _SZ, _VP, _VP]),
     "fmcw_plots_set_grid_for_test": (_I, [_VP, C.c_uint32]),
+    "fmcw_bearings_config_default": (None, [C.POINTER(FmcwBearingsConfig)]),
+    "fmcw_bearings_create": (_I, [C.POINTER(FmcwBearingsConfig), C.POINTER(_VP)]),
+    "fmcw_bearings_destroy": (_I, [_VP]),
+    "fmcw_bearings_enqueue": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _VP, _VP, _VP, _VP, _VP]),
+    "fmcw_bearings_set_grid_for_test": (_I, [_VP, C.c_uint32]),
     "fmcw_tws_config_default": (None, [C.POINTER(FmcwTwsConfig)]),
     "fmcw_tws_create": (_I, [C.POINTER(FmcwTwsConfig), C.POINTER(_VP)]),
     "fmcw_tws_destroy": (_I, [_VP]),

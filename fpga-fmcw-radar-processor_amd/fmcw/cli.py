@@ -19,6 +19,9 @@ Outputs in --out-dir (names the visualizer searches, model/visualize_radar_targe
   ADR_plots.txt (with --plots [--plot-window R D]): one line per plot (local-maximum detection
                  of its R x D window, fmcw.plots): "frame r d mag n_cells r+d_range d+d_doppler";
                  with --plots, --tracks feeds the tracker each frame's plots, not its detections
+  ADR_bearings.txt (with --bearings [--rx-spacing 0.5]): one line per detection (per plot with
+                 --plots): "frame r d power nu sin_theta coherence flags" (fmcw.bearings: the phase
+                 step across the receive channels in cycles per element, and nu / spacing)
 """
 from __future__ import annotations
 
@@ -28,8 +31,9 @@ from pathlib import Path
 import numpy as np
 
 from . import formats, synth
+from .bearings import BearingEstimator
 from .plots import PlotExtractor
-from .radar_core import RadarCore, adc_words_to_cube
+from .radar_core import DeviceBuffer, RadarCore, adc_words_to_cube
 from .tracker import TwsTracker
 
 
@@ -55,7 +59,7 @@ def load_cube(path: Path, ns: int, nc: int):
     raise SystemExit(f"unsupported input {path}")
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("input", type=Path)
     ap.add_argument("--n-range", type=int, default=1024)
@@ -75,12 +79,34 @@ def main(argv=None):
     ap.add_argument("--window", default="hamming", choices=["hamming", "none", "q15_rtl"])
     ap.add_argument("--doppler-centred", action="store_true",
                     help="write Doppler bins fftshifted (zero Doppler at N/2, as the visualizer assumes)")
+    ap.add_argument("--bearings", action="store_true",
+                    help="estimate the bearing of every detection (of every plot with --plots) from the "
+                         "phase across the receive channels, write ADR_bearings.txt")
+    ap.add_argument("--rx-spacing", type=float, default=0.5, metavar="WAVELENGTHS",
+                    help="element spacing of the receive array in wavelengths (with --bearings)")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     a = ap.parse_args(argv)
+    if a.bearings and a.window == "q15_rtl":
+        ap.error("--bearings needs a float window (hamming or none)")
+    if a.bearings and not a.rx_spacing > 0:
+        ap.error("--rx-spacing must be positive")
     cube, dt = load_cube(a.input, a.n_range, a.n_doppler)
-    nf = cube.shape[0]
-    with RadarCore(N_RANGE=a.n_range, N_DOPPLER=a.n_doppler, N_RX=cube.shape[1], in_dtype=dt,
+    nf, nrx = cube.shape[0], cube.shape[1]
+    spec = None
+    with RadarCore(N_RANGE=a.n_range, N_DOPPLER=a.n_doppler, N_RX=nrx, in_dtype=dt,
                    cfar=a.cfar, max_frames=nf, device=a.device, window=a.window) as core:
-        out = core.process(np.ascontiguousarray(cube))
+        cube = np.ascontiguousarray(cube)
+        out = core.process(cube)
+        if a.bearings:   # the corner-turned spectrum still carries the channels' phases
+            dc = DeviceBuffer(cube.nbytes, a.device)
+            dc.upload(cube)
+            spec = DeviceBuffer(nf * nrx * a.n_range * a.n_doppler * 8, a.device)
+            core.range_ct(dc, spec, nf)
+            dc.free()
     a.out_dir.mkdir(parents=True, exist_ok=True)
     det_name = "ADR_quick_det.txt" if a.quick else "ADR_detections.txt"
     n = formats.write_detections(a.out_dir / det_name, out.dets, doppler_centred=a.doppler_centred,
@@ -96,6 +122,14 @@ def main(argv=None):
         formats.write_plots(a.out_dir / "ADR_plots.txt", scans, doppler_centred=a.doppler_centred,
                             n_doppler=a.n_doppler)
         print(f"{len(scans)} plots (window {a.plot_window[0]} x {a.plot_window[1]}) -> {a.out_dir / 'ADR_plots.txt'}")
+    if a.bearings:
+        with BearingEstimator(N_RANGE=a.n_range, N_DOPPLER=a.n_doppler, N_RX=nrx, window=a.window,
+                              spacing=a.rx_spacing, max_records=max(len(scans), 1), device=a.device) as be:
+            bearings, _ = be.estimate(spec, scans, want_snaps=False)
+        spec.free()
+        formats.write_bearings(a.out_dir / "ADR_bearings.txt", bearings, doppler_centred=a.doppler_centred,
+                               n_doppler=a.n_doppler)
+        print(f"{len(bearings)} bearings ({nrx} rx, spacing {a.rx_spacing}) -> {a.out_dir / 'ADR_bearings.txt'}")
     if a.tracks:
         with TwsTracker(rtl_compat=a.tracker_rtl) as trk:
             hist = []

@@ -67,6 +67,30 @@ def read_plots(path) -> np.ndarray:
     return np.array(rows, np.float64).reshape(-1, 7)
 
 
+def write_bearings(path, bearings, doppler_centred: bool = False, n_doppler: int | None = None) -> int:
+    """Write bearings (fmcw.bearings.BEARING_DTYPE) as 'frame r d power nu sin_theta coherence flags'
+    lines: the cell and the flags as integers, power with 9 significant digits (an fp32 value
+    survives the round trip), nu / sin_theta / coherence with 6 decimals."""
+    dop = np.asarray(bearings["doppler"], np.int64)
+    if doppler_centred:
+        if not n_doppler:
+            raise ValueError("doppler_centred needs n_doppler")
+        dop = centre_doppler(dop, n_doppler)
+    with open(path, "w") as f:
+        for i in range(len(bearings)):
+            b = bearings[i]
+            f.write(f"{int(b['frame'])} {int(b['range'])} {int(dop[i])} {float(b['power']):.9g} "
+                    f"{float(b['nu']):.6f} {float(b['sin_theta']):.6f} {float(b['coherence']):.6f} "
+                    f"{int(b['flags'])}\n")
+    return len(bearings)
+
+
+def read_bearings(path) -> np.ndarray:
+    """The 8-column lines of write_bearings as a float64 [n, 8] array."""
+    rows = [[float(x) for x in line.split()] for line in Path(path).read_text().splitlines() if line.split()]
+    return np.array(rows, np.float64).reshape(-1, 8)
+
+
 def read_detections(path) -> np.ndarray:
     """Parse like load_detections() (visualize_radar_targets.py:109-122): 3-token lines only."""
     rows = []

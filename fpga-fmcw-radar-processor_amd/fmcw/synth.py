@@ -8,7 +8,9 @@ saturated to the int16 ADC range, then stored as complex64 / f16 / int16 pairs.
                         (Per-frame RNG: numpy PCG64, seed = seed + frame.)
   recipe "random_target" rtl/src/tb_radar_core.vhd:88-107: one target per frame at
                         r = U*0.88 Ns + 0.05 Ns, d = U*(100/128) Nc, A = 20000, noise +-100.
-  phase offset per rx   2 pi rx 0.25.
+  phase offset per rx   2 pi rx rx_phase: a uniform line array sees a target at rx_phase cycles per
+                        element (a scalar, or one value per target); default 0.25 (SURVEY.md 8d,
+                        config 3), the bearing fmcw.bearings estimates back.
 
 Used by bench.py and the tests; the product path never generates data itself.
 """
@@ -28,17 +30,21 @@ def _targets(recipe: str, ns: int, nc: int, rng: np.random.Generator):
 
 
 def frame(ns: int, nc: int, n_rx: int = 1, recipe: str = "two_targets", seed: int = 1234,
-          dtype: str = "f32") -> np.ndarray:
-    """One frame [rx][chirp][sample] as complex64 (f32), or [rx][chirp][sample][2] f16/int16."""
+          dtype: str = "f32", rx_phase=0.25) -> np.ndarray:
+    """One frame [rx][chirp][sample] as complex64 (f32), or [rx][chirp][sample][2] f16/int16.
+    rx_phase: cycles per element, a scalar or one value per target of the recipe."""
     rng = np.random.Generator(np.random.PCG64(seed))
     tg, noise = _targets(recipe, ns, nc, rng)
+    ph = [float(rx_phase)] * len(tg) if np.ndim(rx_phase) == 0 else [float(p) for p in rx_phase]
+    if len(ph) != len(tg):
+        raise ValueError(f"rx_phase has {len(ph)} values for the {len(tg)} targets of {recipe}")
     n = np.arange(ns)[None, :]
     c = np.arange(nc)[:, None]
     out = np.empty((n_rx, nc, ns), np.complex128)
     for rx in range(n_rx):
         x = np.zeros((nc, ns), np.complex128)
-        for (r, d, a) in tg:
-            x += a * np.exp(2j * np.pi * (r * n / ns + d * c / nc + 0.25 * rx))
+        for (r, d, a), p in zip(tg, ph):
+            x += a * np.exp(2j * np.pi * (r * n / ns + d * c / nc + p * rx))
         x += noise * (rng.uniform(-1, 1, (nc, ns)) + 1j * rng.uniform(-1, 1, (nc, ns)))
         out[rx] = x
     i = np.clip(np.rint(out.real), -32768, 32767)
@@ -53,8 +59,8 @@ def frame(ns: int, nc: int, n_rx: int = 1, recipe: str = "two_targets", seed: in
 
 
 def frames(n_frames: int, ns: int, nc: int, n_rx: int = 1, recipe: str = "two_targets",
-           seed: int = 1234, dtype: str = "f32") -> np.ndarray:
-    return np.stack([frame(ns, nc, n_rx, recipe, seed + f, dtype) for f in range(n_frames)])
+           seed: int = 1234, dtype: str = "f32", rx_phase=0.25) -> np.ndarray:
+    return np.stack([frame(ns, nc, n_rx, recipe, seed + f, dtype, rx_phase) for f in range(n_frames)])
 
 
 def ieee_uniform(seed1: int, seed2: int, n: int):

@@ -84,7 +84,10 @@ extern "C" {
                                signature are unchanged.
                                Still 8 with the grid caps (FMCW_PARAM_GRID_*, FMCW_INFO_GRID_*) and
                                fmcw_plots_set_grid_for_test: new enum values and one new function,
-                               no struct or signature change */
+                               no struct or signature change.
+                               Still 8 with the bearing estimator (fmcw_bearings_*, fmcw_bearing,
+                               fmcw_bearings_config): functions and types of its own, no existing
+                               struct, enum or signature changes */
 
 typedef enum {
   FMCW_OK = 0,
@@ -427,6 +430,94 @@ int fmcw_plots_enqueue(fmcw_plotter* p, const fmcw_det* dets_dev, size_t det_cap
  * over the 1024-record tiles, so that a short list drives a workgroup through several tiles.
  * 0 = the built-in bound (4096), else min(that bound, grid).  Plots never depend on it. */
 int fmcw_plots_set_grid_for_test(fmcw_plotter* p, uint32_t grid);
+
+/* ---- Bearing estimation: rx snapshots and angle per detection ---------------------------
+ * With n_rx > 1 the path integrates the channels non-coherently (FMCW_MAG_ABS) and the phase
+ * across them, which carries a target's angle, is gone from every output of fmcw_enqueue.  The
+ * estimator recomputes, for each record of a detection or plot list, the one Doppler bin of the
+ * one range row per channel from the corner-turned spectrum of fmcw_range_ct (spec
+ * [frame][rx][range][chirp], complex fp32, range window applied, scaled by 2^-range_shift, no
+ * Doppler window) and compares the channels' phases.  It is an object of its own, not part of
+ * fmcw_handle / fmcw_config; the reference (one receive channel) has no such stage.
+ *
+ * Input: a record list and its count word.  A record is any element that begins with
+ * {uint32 frame; uint16 range; uint16 doppler}: fmcw_det (stride 16) or fmcw_plot (stride 32).
+ * Order is free and duplicates are allowed.
+ *
+ * Snapshot of record i = (f, r, d), channel k = 0 .. n_rx - 1:
+ *   s_k = sum_c w[c] y_k[c] exp(-2 pi i d c / n_doppler),   c = 0 .. n_doppler - 1,
+ * y_k the canceller of mti_mode over x_k[c] = spec[f][k][r][c] (OFF: x[c]; 2-pulse: x[c] - x[c-1];
+ * 3-pulse: x[c] - 2 x[c-1] + x[c-2]; the delay line is zero before chirp 0), and w the library's
+ * fp32 Hamming table of n_doppler points (the values fmcw_enqueue multiplies by), or all ones for
+ * FMCW_WIN_NONE.  The float paths only: no Q15 window, no compat MTI.  With the handle's own window
+ * and mti_mode, s_k is the complex value whose magnitude the map holds.
+ *
+ * Bearing, for a uniform line array with element k at k * spacing wavelengths:
+ *   P = sum_{k=0}^{n_rx-2} s_{k+1} conj(s_k)
+ *   nu = arg(P) / (2 pi)        cycles per element, in [-0.5, 0.5] (atan2's +0.5 on the branch cut)
+ *   sin_theta = nu / spacing
+ *   power = sqrt(sum_k |s_k|^2)                  the NCI magnitude of the cell
+ *   coherence = |P| / sum_{k=0}^{n_rx-2} |s_{k+1}| |s_k|   1 for one plane wave, lower when two
+ *                                targets share the cell; 0 if the denominator is 0 or not finite
+ * The closed-form phase comparison, not a scan over an angle grid: O(n_rx), and no argmax to differ
+ * between precisions.  Callers who want more (MUSIC, a Bartlett scan) take the snapshots. */
+#define FMCW_BEARING_NO_ANGLE 1u      /* |sin_theta| > 1: no real angle */
+#define FMCW_BEARING_ONE_RX 2u        /* n_rx == 1: nu = 0, sin_theta = 0, coherence = 0 */
+#define FMCW_BEARING_OUT_OF_RANGE 4u  /* frame >= n_frames of the call, range >= n_range or doppler >=
+                                         n_doppler: no memory is read, every other field of the
+                                         output record (and its snapshot) is zero */
+typedef struct fmcw_bearing {   /* 32 bytes */
+  uint32_t frame;              /* the record's cell, copied (zero with FMCW_BEARING_OUT_OF_RANGE) */
+  uint16_t range;
+  uint16_t doppler;
+  uint32_t flags;              /* FMCW_BEARING_* bits */
+  float nu;
+  float sin_theta;
+  float power;
+  float coherence;
+  uint32_t reserved;           /* written as 0 */
+} fmcw_bearing;
+typedef struct fmcw_bearings_config {   /* 32 bytes */
+  uint32_t n_range;            /* as fmcw_config: power of two, 64..8192 */
+  uint32_t n_doppler;          /* as fmcw_config: power of two, 32..1024 */
+  uint32_t n_rx;               /* 1..64 */
+  int32_t window;              /* FMCW_WIN_NONE or FMCW_WIN_HAMMING */
+  int32_t mti_mode;            /* fmcw_mti_mode */
+  float spacing;               /* element spacing in wavelengths, > 0 and finite */
+  uint32_t max_records;        /* most records one call processes, 1..2^31-1 (no scratch depends on it) */
+                               /* device memory of an estimator: 12 B per Doppler bin + 8 KiB */
+  int32_t device_id;           /* 0..63 */
+} fmcw_bearings_config;
+typedef struct fmcw_bearings fmcw_bearings;
+/* Status words of fmcw_bearings_enqueue (n_out_dev). */
+#define FMCW_BEARING_STATUS_WORDS 2
+/* Defaults: 1024, 128, 1 rx, Hamming, MTI off, spacing 0.5, max_records 2^20, device 0. */
+void fmcw_bearings_config_default(fmcw_bearings_config* cfg);
+/* Validates before any device access (FMCW_EINVAL, the message names the field), then
+ * FMCW_ENODEV / FMCW_ENOMEM as fmcw_create.  Uploads the twiddle and window tables (n_doppler
+ * entries each, computed in fp64). */
+int fmcw_bearings_create(const fmcw_bearings_config* cfg, fmcw_bearings** out);
+int fmcw_bearings_destroy(fmcw_bearings* b);   /* NULL is FMCW_OK */
+/* Device pointers only; stream-ordered, allocates nothing, never synchronises and keeps no state
+ * between calls, so it can be captured into a hipGraph after fmcw_range_ct and fmcw_enqueue on the
+ * same stream and replayed.  One stream at a time per estimator (its 8 KiB of per-workgroup
+ * counts are shared by its calls).
+ * spec_dev: n_frames frames as fmcw_range_ct writes them for (n_range, n_doppler, n_rx).
+ * records_dev: rec_cap records of rec_stride bytes (16 or 32, else FMCW_EINVAL), 4-byte aligned.
+ * Processes n = min(n_records_dev[0], rec_cap, max_records) records (n is read on the device):
+ *   bearings_dev[i], i < n (16-byte aligned, room for min(rec_cap, max_records) records); nothing
+ *                  is stored beyond them,
+ *   snaps_dev[i * n_rx + k] = s_k as complex fp32 (8-byte aligned), unless snaps_dev is NULL,
+ *   n_out_dev[0] = n, n_out_dev[1] = the out-of-range records among them.
+ * With n = 0 it writes {0, 0} and touches nothing else. */
+int fmcw_bearings_enqueue(fmcw_bearings* b, const void* spec_dev, size_t n_frames,
+                          const void* records_dev, size_t rec_stride, size_t rec_cap,
+                          const uint32_t* n_records_dev, fmcw_bearing* bearings_dev, void* snaps_dev,
+                          uint32_t* n_out_dev, void* stream);
+/* Test hook: bounds the workgroups of the estimator's kernel, whose waves stride over the records,
+ * so that a short list drives a workgroup through several records.  0 = the built-in bound (2048),
+ * else min(that bound, grid).  Results never depend on it. */
+int fmcw_bearings_set_grid_for_test(fmcw_bearings* b, uint32_t grid);
 
 /* ---- Track-while-scan tracker (host side) ----------------------------------------------
  * Replaces rtl/src/tws_tracker.vhd (radar_core.vhd:424-438): MAX_TRACKS alpha-beta tracks in

@@ -1,0 +1,97 @@
+#!/usr/bin/env python3
+"""Time the bearing estimator (fmcw_bearings_enqueue) on the bench's detection lists.
+
+Builds each workload's detection list once through the whole path (bench.py's synthetic frames,
+fmcw_enqueue with per-kernel profiling on) and its corner-turned spectrum with fmcw_range_ct, then
+times fmcw_bearings_enqueue on that list with stream events (3 warm-up calls, then --iters calls
+between two events) and prints one JSON line per (workload, scale override): the mean time per call,
+the records, the bytes of spectrum rows the call reads (records x n_rx x n_doppler x 8) over that
+time, and -- as the yardstick -- the FMCW_K_COMPACT time of the call that produced the list.  Also
+the cost of the extra fmcw_range_ct pass beside fmcw_enqueue alone on the same handle.
+usage: python tools/bearings_bench.py [--cases c3:0,c3:1] [--frames 4] [--iters 20] [--no-snaps]
+(a case is workload:cfar_scale_ovr; ovr 1 is the reference's dense list, ~27 % of all cells)"""
+import argparse
+import json
+import sys
+from pathlib import Path
+
+REPO = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(REPO / "fpga-fmcw-radar-processor_amd"))
+
+GEOM = {"c3": dict(ns=4096, nc=512, nrx=4), "c2x4": dict(ns=1024, nc=256, nrx=4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", default="c3:0,c3:1")
+    ap.add_argument("--frames", type=int, default=4)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--no-snaps", action="store_true", help="pass snaps_dev = NULL")
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+    from fmcw import BearingEstimator, RadarCore, synth
+
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+
+    def timed(fn, iters):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return 1e3 * e0.elapsed_time(e1) / iters     # us per call
+
+    for case in a.cases.split(","):
+        w, ovr = case.split(":")
+        g, ovr, F = GEOM[w], int(ovr), a.frames
+        ns, nc, nrx = g["ns"], g["nc"], g["nrx"]
+        u = synth.frames(F, ns, nc, nrx, "two_targets", seed=1234).view(np.float32)
+        cube = torch.from_numpy(np.ascontiguousarray(u)).to(dev)
+        cap = F * ns * nc if ovr else F * 65536
+        dets = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+        nd = torch.zeros(4, dtype=torch.int32, device=dev)
+        spec = torch.empty((F, nrx, ns, nc, 2), dtype=torch.float32, device=dev)
+        with RadarCore(N_RANGE=ns, N_DOPPLER=nc, N_RX=nrx, cfar="os2d", max_frames=F, cfar_scale_ovr=ovr) as core:
+            core.enqueue(cube, F, None, dets, cap, nd, stream=stream)   # warm-up
+            torch.cuda.synchronize()
+            core.set_profiling(True)
+            core.reset_kernel_times()
+            for _ in range(3):
+                core.enqueue(cube, F, None, dets, cap, nd, stream=stream)
+            torch.cuda.synchronize()
+            kt = core.kernel_times()
+            core.set_profiling(False)
+            enq_us = timed(lambda: core.enqueue(cube, F, None, dets, cap, nd, stream=stream), a.iters)
+            ct_us = timed(lambda: core.range_ct(cube, spec, F, stream=stream), a.iters)
+        del cube
+        compact_us = 1e3 * kt["k_compact"][0] / 3
+        n = int(nd[0].item())
+        assert 0 < n <= cap and int(nd[1].item()) == 0, nd
+        out = torch.empty((n, 8), dtype=torch.int32, device=dev)
+        snaps = None if a.no_snaps else torch.empty((n, nrx, 2), dtype=torch.float32, device=dev)
+        st = torch.zeros(2, dtype=torch.int32, device=dev)
+        with BearingEstimator(ns, nc, nrx, max_records=n) as be:
+            us = timed(lambda: be.enqueue(spec, F, dets, 16, cap, nd, out, snaps, st, stream=stream), a.iters)
+        assert int(st[0].item()) == n and int(st[1].item()) == 0, st
+        nu = out[:, 3].view(torch.float32)
+        power = out[:, 5].view(torch.float32)
+        strong = power > 0.5 * power.max()
+        row_bytes = n * nrx * nc * 8
+        print(json.dumps({"workload": w, "ovr": ovr, "frames": F, "n_records": n, "snaps": snaps is not None,
+                          "bearings_us_per_call": round(us, 1), "k_compact_us_per_call": round(compact_us, 1),
+                          "ratio": round(us / max(compact_us, 1e-9), 2), "ns_per_record": round(1e3 * us / n, 2),
+                          "row_bytes": row_bytes, "row_read_GBps": round(row_bytes / us / 1e3, 1),
+                          "enqueue_us_per_call": round(enq_us, 1), "range_ct_us_per_call": round(ct_us, 1),
+                          "range_ct_over_enqueue": round(ct_us / enq_us, 3),
+                          "median_nu_of_strong_cells": round(float(nu[strong].median().item()), 4)}), flush=True)
+        del dets, spec, out, snaps
+
+
+if __name__ == "__main__":
+    main()
