@@ -94,6 +94,12 @@ class FmcwBearingsConfig(C.Structure):
                 ("max_records", C.c_uint32), ("device_id", C.c_int32)]
 
 
+class FmcwBeamsConfig(C.Structure):
+    _fields_ = [("n_range", C.c_uint32), ("n_doppler", C.c_uint32), ("n_rx", C.c_uint32),
+                ("n_beams", C.c_uint32), ("window", C.c_int32), ("mti_mode", C.c_int32),
+                ("reserved", C.c_uint32), ("device_id", C.c_int32)]
+
+
 class FmcwTwsConfig(C.Structure):
     _fields_ = [("max_tracks", C.c_uint32), ("max_dets", C.c_uint32), ("init_hits", C.c_uint32),
                 ("coast_max", C.c_uint32), ("gate_r", C.c_uint32), ("gate_d", C.c_uint32),
@@ -148,6 +154,11 @@ SIGNATURES = {
     "fmcw_bearings_destroy": (_I, [_VP]),
     "fmcw_bearings_enqueue": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _VP, _VP, _VP, _VP, _VP]),
     "fmcw_bearings_set_grid_for_test": (_I, [_VP, C.c_uint32]),
+    "fmcw_beams_config_default": (None, [C.POINTER(FmcwBeamsConfig)]),
+    "fmcw_beams_create": (_I, [C.POINTER(FmcwBeamsConfig), _VP, C.POINTER(_VP)]),
+    "fmcw_beams_destroy": (_I, [_VP]),
+    "fmcw_beams_enqueue": (_I, [_VP, _VP, _SZ, _VP, _VP]),
+    "fmcw_beams_set_grid_for_test": (_I, [_VP, C.c_uint32]),
     "fmcw_tws_config_default": (None, [C.POINTER(FmcwTwsConfig)]),
     "fmcw_tws_create": (_I, [C.POINTER(FmcwTwsConfig), C.POINTER(_VP)]),
     "fmcw_tws_destroy": (_I, [_VP]),

@@ -22,6 +22,9 @@ Outputs in --out-dir (names the visualizer searches, model/visualize_radar_targe
   ADR_bearings.txt (with --bearings [--rx-spacing 0.5]): one line per detection (per plot with
                  --plots): "frame r d power nu sin_theta coherence flags" (fmcw.bearings: the phase
                  step across the receive channels in cycles per element, and nu / spacing)
+  ADR_beam_detections.txt (with --beams B [--rx-spacing 0.5]): the channels summed coherently into B
+                 beams at nu_b = (b - B/2) / B cycles per element (fmcw.beams), the CFAR run on every
+                 beam's map: "frame beam r d mag threshold nu_b sin_theta_b" per detection
 """
 from __future__ import annotations
 
@@ -31,9 +34,10 @@ from pathlib import Path
 import numpy as np
 
 from . import formats, synth
+from .beams import BeamFormer, steering_weights
 from .bearings import BearingEstimator
 from .plots import PlotExtractor
-from .radar_core import DeviceBuffer, RadarCore, adc_words_to_cube
+from .radar_core import DET_DTYPE, DeviceBuffer, RadarCore, adc_words_to_cube
 from .tracker import TwsTracker
 
 
@@ -83,8 +87,38 @@ def build_parser():
                     help="estimate the bearing of every detection (of every plot with --plots) from the "
                          "phase across the receive channels, write ADR_bearings.txt")
     ap.add_argument("--rx-spacing", type=float, default=0.5, metavar="WAVELENGTHS",
-                    help="element spacing of the receive array in wavelengths (with --bearings)")
+                    help="element spacing of the receive array in wavelengths (with --bearings, --beams)")
+    ap.add_argument("--beams", type=int, default=0, metavar="B",
+                    help="sum the receive channels coherently into B beams (1..64) at (b - B/2) / B cycles per "
+                         "element, run the CFAR on every beam's map, write ADR_beam_detections.txt")
     return ap
+
+
+def beam_detections(core_args: dict, spec, nf: int, nrx: int, n_beams: int, window: str, device: int):
+    """The CFAR of `core_args` over the n_frames * n_beams beamformed maps of the device spectrum
+    `spec`: (detections with frame = f * n_beams + b, the beams' nu)."""
+    ns, nc = core_args["N_RANGE"], core_args["N_DOPPLER"]
+    nus = (np.arange(n_beams) - n_beams // 2) / n_beams
+    n_maps = nf * n_beams
+    maps = DeviceBuffer(n_maps * ns * nc * 4, device)
+    with BeamFormer(ns, nc, nrx, steering_weights(nrx, nus), window=window, device=device) as bf:
+        bf.enqueue(spec, nf, maps)
+    dn = DeviceBuffer(16, device)
+    with RadarCore(N_RX=1, max_frames=n_maps, **core_args) as core:   # the CFAR stage alone: it sees maps only
+        cap = n_maps * 4096
+        while True:
+            dd = DeviceBuffer(cap * DET_DTYPE.itemsize, device)
+            core.cfar(maps, n_maps, dd, cap, dn)
+            found = int(dn.download(np.uint32, (4,))[0])
+            if found <= cap:
+                dets = dd.download(DET_DTYPE, (found,))
+                dd.free()
+                break
+            dd.free()
+            cap = found
+    maps.free()
+    dn.free()
+    return dets, nus
 
 
 def main(argv=None):
@@ -92,16 +126,24 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.bearings and a.window == "q15_rtl":
         ap.error("--bearings needs a float window (hamming or none)")
-    if a.bearings and not a.rx_spacing > 0:
+    if (a.bearings or a.beams) and not a.rx_spacing > 0:
         ap.error("--rx-spacing must be positive")
+    if a.beams and a.window == "q15_rtl":
+        ap.error("--beams needs a float window (hamming or none)")
+    if a.beams and not 1 <= a.beams <= 64:
+        ap.error("--beams must be in 1..64")
+    if a.beams and a.cfar == "none":
+        ap.error("--beams needs a CFAR (os1d or os2d) to run on the beams' maps")
     cube, dt = load_cube(a.input, a.n_range, a.n_doppler)
     nf, nrx = cube.shape[0], cube.shape[1]
+    if a.beams and nrx < 2:
+        ap.error(f"--beams needs multi-rx input ({a.input} has one channel)")
     spec = None
     with RadarCore(N_RANGE=a.n_range, N_DOPPLER=a.n_doppler, N_RX=nrx, in_dtype=dt,
                    cfar=a.cfar, max_frames=nf, device=a.device, window=a.window) as core:
         cube = np.ascontiguousarray(cube)
         out = core.process(cube)
-        if a.bearings:   # the corner-turned spectrum still carries the channels' phases
+        if a.bearings or a.beams:   # the corner-turned spectrum still carries the channels' phases
             dc = DeviceBuffer(cube.nbytes, a.device)
             dc.upload(cube)
             spec = DeviceBuffer(nf * nrx * a.n_range * a.n_doppler * 8, a.device)
@@ -126,10 +168,18 @@ def main(argv=None):
         with BearingEstimator(N_RANGE=a.n_range, N_DOPPLER=a.n_doppler, N_RX=nrx, window=a.window,
                               spacing=a.rx_spacing, max_records=max(len(scans), 1), device=a.device) as be:
             bearings, _ = be.estimate(spec, scans, want_snaps=False)
-        spec.free()
         formats.write_bearings(a.out_dir / "ADR_bearings.txt", bearings, doppler_centred=a.doppler_centred,
                                n_doppler=a.n_doppler)
         print(f"{len(bearings)} bearings ({nrx} rx, spacing {a.rx_spacing}) -> {a.out_dir / 'ADR_bearings.txt'}")
+    if a.beams:
+        bdets, nus = beam_detections(dict(N_RANGE=a.n_range, N_DOPPLER=a.n_doppler, cfar=a.cfar, device=a.device),
+                                     spec, nf, nrx, a.beams, a.window, a.device)
+        formats.write_beam_detections(a.out_dir / "ADR_beam_detections.txt", bdets, nus, spacing=a.rx_spacing,
+                                      doppler_centred=a.doppler_centred, n_doppler=a.n_doppler)
+        print(f"{len(bdets)} detections in {a.beams} beams ({nrx} rx, spacing {a.rx_spacing}) -> "
+              f"{a.out_dir / 'ADR_beam_detections.txt'}")
+    if spec is not None:
+        spec.free()
     if a.tracks:
         with TwsTracker(rtl_compat=a.tracker_rtl) as trk:
             hist = []

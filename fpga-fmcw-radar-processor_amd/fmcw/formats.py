@@ -91,6 +91,34 @@ def read_bearings(path) -> np.ndarray:
     return np.array(rows, np.float64).reshape(-1, 8)
 
 
+def write_beam_detections(path, dets, nus, spacing: float = 0.5, doppler_centred: bool = False,
+                          n_doppler: int | None = None) -> int:
+    """Write the detections of beamformed maps (fmcw.beams: a record's frame is f * n_beams + b, n_beams
+    = len(nus)) as 'frame beam r d mag threshold nu_b sin_theta_b' lines: the cell as integers, mag and
+    threshold with 9 significant digits (the fp32 values survive the round trip), the beam's nu (cycles
+    per element) and nu / spacing with 6 decimals."""
+    nus = np.asarray(nus, np.float64)
+    nb = len(nus)
+    dop = np.asarray(dets["doppler"], np.int64)
+    if doppler_centred:
+        if not n_doppler:
+            raise ValueError("doppler_centred needs n_doppler")
+        dop = centre_doppler(dop, n_doppler)
+    with open(path, "w") as f:
+        for i in range(len(dets)):
+            d = dets[i]
+            fr, b = divmod(int(d["frame"]), nb)
+            f.write(f"{fr} {b} {int(d['range'])} {int(dop[i])} {float(d['mag']):.9g} {float(d['threshold']):.9g} "
+                    f"{nus[b]:.6f} {nus[b] / spacing:.6f}\n")
+    return len(dets)
+
+
+def read_beam_detections(path) -> np.ndarray:
+    """The 8-column lines of write_beam_detections as a float64 [n, 8] array."""
+    rows = [[float(x) for x in line.split()] for line in Path(path).read_text().splitlines() if line.split()]
+    return np.array(rows, np.float64).reshape(-1, 8)
+
+
 def read_detections(path) -> np.ndarray:
     """Parse like load_detections() (visualize_radar_targets.py:109-122): 3-token lines only."""
     rows = []

@@ -87,7 +87,9 @@ extern "C" {
                                no struct or signature change.
                                Still 8 with the bearing estimator (fmcw_bearings_*, fmcw_bearing,
                                fmcw_bearings_config): functions and types of its own, no existing
-                               struct, enum or signature changes */
+                               struct, enum or signature changes.
+                               Still 8 with the beamformer (fmcw_beams_*, fmcw_beams_config):
+                               functions and types of its own, nothing existing changes */
 
 typedef enum {
   FMCW_OK = 0,
@@ -518,6 +520,69 @@ int fmcw_bearings_enqueue(fmcw_bearings* b, const void* spec_dev, size_t n_frame
  * so that a short list drives a workgroup through several records.  0 = the built-in bound (2048),
  * else min(that bound, grid).  Results never depend on it. */
 int fmcw_bearings_set_grid_for_test(fmcw_bearings* b, uint32_t grid);
+
+/* ---- Coherent beamforming: per-beam range-Doppler maps from the rx channels --------------
+ * With n_rx > 1 fmcw_enqueue sums the channels' powers (FMCW_MAG_ABS: sqrt(sum_rx |X_rx|^2)), which
+ * gains about sqrt(n_rx) in SNR.  The beamformer applies a complex weight matrix to the channels of
+ * fmcw_range_ct's spectrum BEFORE the Doppler transform, so a beam steered at a target gains n_rx,
+ * and two targets that share a range-Doppler cell separate in angle.  Its maps go to fmcw_cfar as
+ * any caller-supplied map does.  An object of its own, not part of fmcw_handle / fmcw_config; the
+ * reference (one receive channel) has no such stage.
+ *
+ * For frame f, beam b, range row r:
+ *   y_b[c] = sum_{k=0}^{n_rx-1} W[b][k] x_k[c],   x_k[c] = spec[f][k][r][c]
+ * (spec as fmcw_range_ct writes it: complex fp32, range window applied, no Doppler window),
+ *   z_b = the canceller of mti_mode over y_b, as the bearing estimator defines it (OFF: y[c];
+ *         2-pulse: y[c] - y[c-1]; 3-pulse: y[c] - 2 y[c-1] + y[c-2]; zero delay line before chirp 0),
+ *   maps[f][b][r][d] = | sum_c w[c] z_b[c] exp(-2 pi i d c / n_doppler) |,
+ * w the library's fp32 Hamming table of n_doppler points (the values fmcw_enqueue multiplies by), or
+ * all ones for FMCW_WIN_NONE.  The float paths only: no Q15 window, no compat MTI, no AMBM, no dB map.
+ * Window and canceller are linear per chirp: the kernel may apply them per channel or per beam; this
+ * header defines the result, not the order.  The channels are summed in the order k = 0 .. n_rx - 1,
+ * so a map's bytes depend on spec and W alone.
+ *
+ * Weights: weights_host holds n_beams x n_rx complex fp32 values, interleaved re, im, row-major
+ * [beam][rx], copied to the device at create (no update afterwards); every component must be finite.
+ * Steering, taper and channel calibration are the caller's: the library applies the matrix and
+ * nothing else.  With n_rx == 1 and W = [[1]] the map is fmcw_enqueue's single-channel linear map
+ * for the same window and mti_mode.
+ *
+ * Layout: maps_dev is [frame][beam][range][doppler] float32, 16-byte aligned.  Each (frame, beam)
+ * map is contiguous, so fmcw_cfar(h, maps_dev, n_frames * n_beams, ...) runs on it unchanged with a
+ * handle whose max_frames >= n_frames * n_beams; a detection's .frame is then f * n_beams + b. */
+typedef struct fmcw_beams_config {   /* 32 bytes */
+  uint32_t n_range;            /* as fmcw_config: power of two, 64..8192 */
+  uint32_t n_doppler;          /* as fmcw_config: power of two, 32..1024 */
+  uint32_t n_rx;               /* 1..64 */
+  uint32_t n_beams;            /* 1..64 */
+  int32_t window;              /* FMCW_WIN_NONE or FMCW_WIN_HAMMING (Doppler window) */
+  int32_t mti_mode;            /* fmcw_mti_mode */
+  uint32_t reserved;           /* must be 0 */
+                               /* device memory of a beamformer: the weight matrix (8 B x n_beams x
+                                  n_rx) and the window table (4 B per Doppler bin), nothing else */
+  int32_t device_id;           /* 0..63 */
+} fmcw_beams_config;
+typedef struct fmcw_beams fmcw_beams;
+/* Defaults: 1024, 128, 1 rx, 1 beam, Hamming, MTI off, device 0. */
+void fmcw_beams_config_default(fmcw_beams_config* cfg);
+/* Validates cfg and weights_host before any device access (FMCW_EINVAL, the message names the
+ * field), then FMCW_ENODEV / FMCW_ENOMEM as fmcw_bearings_create.  Uploads the weights and the
+ * window table. */
+int fmcw_beams_create(const fmcw_beams_config* cfg, const float* weights_host, fmcw_beams** out);
+int fmcw_beams_destroy(fmcw_beams* b);   /* NULL is FMCW_OK */
+/* Device pointers only; stream-ordered, allocates nothing, never synchronises and keeps no state
+ * between calls (it has no scratch), so it can be captured into a hipGraph after fmcw_range_ct on
+ * the same stream and replayed.  One stream at a time per beamformer.
+ * spec_dev: n_frames frames as fmcw_range_ct writes them for (n_range, n_doppler, n_rx).
+ * maps_dev: n_frames * n_beams maps (above); nothing is stored beyond them.
+ * n_frames == 0 is FMCW_OK and launches nothing. */
+int fmcw_beams_enqueue(fmcw_beams* b, const void* spec_dev, size_t n_frames, float* maps_dev,
+                       void* stream);
+/* Test hook: bounds the workgroups of the beamformer's persistent kernel, whose waves stride over the
+ * tiles of 1024 map cells, so that a small call drives a workgroup through several tiles, frames and
+ * beams.  0 = the built-in bound (the workgroups resident at once), else min(that bound, grid).
+ * Results never depend on it. */
+int fmcw_beams_set_grid_for_test(fmcw_beams* b, uint32_t grid);
 
 /* ---- Track-while-scan tracker (host side) ----------------------------------------------
  * Replaces rtl/src/tws_tracker.vhd (radar_core.vhd:424-438): MAX_TRACKS alpha-beta tracks in
