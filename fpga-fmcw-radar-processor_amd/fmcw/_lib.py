@@ -42,6 +42,7 @@ RANGE_KERNELS = ("k_range", "k_range2 (retired)", "k_range_sq", "k_range_px")
 STATUS_WORDS = 4      # FMCW_STATUS_WORDS: n_dets_dev = found, lost, window / word saturations
 PLOT_STATUS_WORDS = 2  # FMCW_PLOT_STATUS_WORDS: n_plots_dev = plots found, records not examined
 BEARING_STATUS_WORDS = 2  # FMCW_BEARING_STATUS_WORDS: n_out_dev = records processed, out of range
+CACFAR_CA, CACFAR_GO, CACFAR_SO = 0, 1, 2   # fmcw_cacfar_mode
 BEARING_NO_ANGLE, BEARING_ONE_RX, BEARING_OUT_OF_RANGE = 1, 2, 4   # fmcw_bearing.flags bits
 
 STATUS_NAMES = {0: "FMCW_OK", -1: "FMCW_EINVAL", -2: "FMCW_ENOMEM", -3: "FMCW_EHIP",
@@ -98,6 +99,13 @@ class FmcwBeamsConfig(C.Structure):
     _fields_ = [("n_range", C.c_uint32), ("n_doppler", C.c_uint32), ("n_rx", C.c_uint32),
                 ("n_beams", C.c_uint32), ("window", C.c_int32), ("mti_mode", C.c_int32),
                 ("reserved", C.c_uint32), ("device_id", C.c_int32)]
+
+
+class FmcwCaCfarConfig(C.Structure):
+    _fields_ = [("n_range", C.c_uint32), ("n_doppler", C.c_uint32), ("mode", C.c_int32),
+                ("ref_range", C.c_uint32), ("guard_range", C.c_uint32), ("ref_doppler", C.c_uint32),
+                ("guard_doppler", C.c_uint32), ("alpha", C.c_float), ("max_frames", C.c_uint32),
+                ("device_id", C.c_int32), ("reserved", C.c_uint32 * 2)]
 
 
 class FmcwTwsConfig(C.Structure):
@@ -159,6 +167,11 @@ SIGNATURES = {
     "fmcw_beams_destroy": (_I, [_VP]),
     "fmcw_beams_enqueue": (_I, [_VP, _VP, _SZ, _VP, _VP]),
     "fmcw_beams_set_grid_for_test": (_I, [_VP, C.c_uint32]),
+    "fmcw_cacfar_config_default": (None, [C.POINTER(FmcwCaCfarConfig)]),
+    "fmcw_cacfar_create": (_I, [C.POINTER(FmcwCaCfarConfig), C.POINTER(_VP)]),
+    "fmcw_cacfar_destroy": (_I, [_VP]),
+    "fmcw_cacfar_enqueue": (_I, [_VP, _VP, _SZ, _VP, _SZ, _VP, _VP]),
+    "fmcw_cacfar_set_grid_for_test": (_I, [_VP, C.c_uint32]),
     "fmcw_tws_config_default": (None, [C.POINTER(FmcwTwsConfig)]),
     "fmcw_tws_create": (_I, [C.POINTER(FmcwTwsConfig), C.POINTER(_VP)]),
     "fmcw_tws_destroy": (_I, [_VP]),

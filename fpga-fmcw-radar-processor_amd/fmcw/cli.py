@@ -1,6 +1,6 @@
 """fmcw CLI -- run the MI355X hot path on a file and write the reference's output formats.
 
-    python -m fmcw.cli INPUT [--n-range 1024 --n-doppler 128 --cfar os2d|os1d|none]
+    python -m fmcw.cli INPUT [--n-range 1024 --n-doppler 128 --cfar os2d|os1d|ca|go|so|none]
                              [--out-dir DIR] [--quick] [--map-file radar_output.txt]
 
 INPUT formats (by extension):
@@ -14,6 +14,8 @@ Outputs in --out-dir (names the visualizer searches, model/visualize_radar_targe
   ADR_detections.txt (or ADR_quick_det.txt with --quick): "r d mag" per detection
   radar_output.txt (with --map-file): "r d 0 0 mag" map of the first frame
   --doppler-centred shifts Doppler bins by N/2 (fftshift) in both files
+  --cfar ca|go|so [--ca-alpha 4] detects with the cell-averaging family (fmcw.cacfar: CA, greatest-of,
+                 smallest-of; the 2-D window 4/1/4/2) on the map of the path run without a CFAR
   ADR_tracks.txt (with --tracks): the track-while-scan log, one scan per frame
                  ("TRK id R= D= Q=" / "SCAN_END ACTIVE=n", tb_radar_core.vhd:163-180)
   ADR_plots.txt (with --plots [--plot-window R D]): one line per plot (local-maximum detection
@@ -31,10 +33,13 @@ from __future__ import annotations
 import argparse
 from pathlib import Path
 
+import math
+
 import numpy as np
 
 from . import formats, synth
 from .beams import BeamFormer, steering_weights
+from .cacfar import CaCfar
 from .bearings import BearingEstimator
 from .plots import PlotExtractor
 from .radar_core import DET_DTYPE, DeviceBuffer, RadarCore, adc_words_to_cube
@@ -68,7 +73,9 @@ def build_parser():
     ap.add_argument("input", type=Path)
     ap.add_argument("--n-range", type=int, default=1024)
     ap.add_argument("--n-doppler", type=int, default=128)
-    ap.add_argument("--cfar", default="os2d", choices=["os2d", "os1d", "none"])
+    ap.add_argument("--cfar", default="os2d", choices=["os2d", "os1d", "ca", "go", "so", "none"])
+    ap.add_argument("--ca-alpha", type=float, default=4.0, metavar="ALPHA",
+                    help="threshold factor of --cfar ca / go / so (finite, > 0)")
     ap.add_argument("--out-dir", type=Path, default=Path("."))
     ap.add_argument("--quick", action="store_true", help="write ADR_quick_det.txt (128x32 geometry)")
     ap.add_argument("--map-file", default=None)
@@ -94,7 +101,11 @@ def build_parser():
     return ap
 
 
-def beam_detections(core_args: dict, spec, nf: int, nrx: int, n_beams: int, window: str, device: int):
+CA_MODES = ("ca", "go", "so")
+
+
+def beam_detections(core_args: dict, spec, nf: int, nrx: int, n_beams: int, window: str, device: int,
+                    ca_alpha: float = 4.0):
     """The CFAR of `core_args` over the n_frames * n_beams beamformed maps of the device spectrum
     `spec`: (detections with frame = f * n_beams + b, the beams' nu)."""
     ns, nc = core_args["N_RANGE"], core_args["N_DOPPLER"]
@@ -103,6 +114,11 @@ def beam_detections(core_args: dict, spec, nf: int, nrx: int, n_beams: int, wind
     maps = DeviceBuffer(n_maps * ns * nc * 4, device)
     with BeamFormer(ns, nc, nrx, steering_weights(nrx, nus), window=window, device=device) as bf:
         bf.enqueue(spec, nf, maps)
+    if core_args["cfar"] in CA_MODES:
+        with CaCfar(ns, nc, mode=core_args["cfar"], alpha=ca_alpha, max_frames=n_maps, device=device) as ca:
+            dets = ca.detect(maps)
+        maps.free()
+        return dets, nus
     dn = DeviceBuffer(16, device)
     with RadarCore(N_RX=1, max_frames=n_maps, **core_args) as core:   # the CFAR stage alone: it sees maps only
         cap = n_maps * 4096
@@ -134,13 +150,16 @@ def main(argv=None):
         ap.error("--beams must be in 1..64")
     if a.beams and a.cfar == "none":
         ap.error("--beams needs a CFAR (os1d or os2d) to run on the beams' maps")
+    if not (math.isfinite(a.ca_alpha) and a.ca_alpha > 0):
+        ap.error("--ca-alpha must be finite and positive")
+    ca = a.cfar in CA_MODES
     cube, dt = load_cube(a.input, a.n_range, a.n_doppler)
     nf, nrx = cube.shape[0], cube.shape[1]
     if a.beams and nrx < 2:
         ap.error(f"--beams needs multi-rx input ({a.input} has one channel)")
     spec = None
     with RadarCore(N_RANGE=a.n_range, N_DOPPLER=a.n_doppler, N_RX=nrx, in_dtype=dt,
-                   cfar=a.cfar, max_frames=nf, device=a.device, window=a.window) as core:
+                   cfar="none" if ca else a.cfar, max_frames=nf, device=a.device, window=a.window) as core:
         cube = np.ascontiguousarray(cube)
         out = core.process(cube)
         if a.bearings or a.beams:   # the corner-turned spectrum still carries the channels' phases
@@ -149,18 +168,22 @@ def main(argv=None):
             spec = DeviceBuffer(nf * nrx * a.n_range * a.n_doppler * 8, a.device)
             core.range_ct(dc, spec, nf)
             dc.free()
+    dets = out.dets
+    if ca:   # the cell-averaging detector on the path's map
+        with CaCfar(a.n_range, a.n_doppler, mode=a.cfar, alpha=a.ca_alpha, max_frames=nf, device=a.device) as det:
+            dets = det.detect(out.rd_map)
     a.out_dir.mkdir(parents=True, exist_ok=True)
     det_name = "ADR_quick_det.txt" if a.quick else "ADR_detections.txt"
-    n = formats.write_detections(a.out_dir / det_name, out.dets, doppler_centred=a.doppler_centred,
+    n = formats.write_detections(a.out_dir / det_name, dets, doppler_centred=a.doppler_centred,
                                  n_doppler=a.n_doppler)
     if a.map_file:
         formats.write_rd_map(a.out_dir / a.map_file, out.rd_map[0], doppler_centred=a.doppler_centred)
     print(f"{nf} frame(s) {a.n_doppler}x{a.n_range}: {n} detections -> {a.out_dir / det_name}")
-    scans = out.dets
+    scans = dets
     if a.plots:
         with PlotExtractor(N_RANGE=a.n_range, N_DOPPLER=a.n_doppler, win=tuple(a.plot_window),
-                           max_dets=max(len(out.dets), 1), device=a.device) as px:
-            scans = px.extract(out.dets)
+                           max_dets=max(len(dets), 1), device=a.device) as px:
+            scans = px.extract(dets)
         formats.write_plots(a.out_dir / "ADR_plots.txt", scans, doppler_centred=a.doppler_centred,
                             n_doppler=a.n_doppler)
         print(f"{len(scans)} plots (window {a.plot_window[0]} x {a.plot_window[1]}) -> {a.out_dir / 'ADR_plots.txt'}")
@@ -173,7 +196,7 @@ def main(argv=None):
         print(f"{len(bearings)} bearings ({nrx} rx, spacing {a.rx_spacing}) -> {a.out_dir / 'ADR_bearings.txt'}")
     if a.beams:
         bdets, nus = beam_detections(dict(N_RANGE=a.n_range, N_DOPPLER=a.n_doppler, cfar=a.cfar, device=a.device),
-                                     spec, nf, nrx, a.beams, a.window, a.device)
+                                     spec, nf, nrx, a.beams, a.window, a.device, a.ca_alpha)
         formats.write_beam_detections(a.out_dir / "ADR_beam_detections.txt", bdets, nus, spacing=a.rx_spacing,
                                       doppler_centred=a.doppler_centred, n_doppler=a.n_doppler)
         print(f"{len(bdets)} detections in {a.beams} beams ({nrx} rx, spacing {a.rx_spacing}) -> "

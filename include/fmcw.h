@@ -89,7 +89,10 @@ extern "C" {
                                fmcw_bearings_config): functions and types of its own, no existing
                                struct, enum or signature changes.
                                Still 8 with the beamformer (fmcw_beams_*, fmcw_beams_config):
-                               functions and types of its own, nothing existing changes */
+                               functions and types of its own, nothing existing changes.
+                               Still 8 with the cell-averaging detector (fmcw_cacfar_*,
+                               fmcw_cacfar_config): functions and types of its own, nothing
+                               existing changes */
 
 typedef enum {
   FMCW_OK = 0,
@@ -583,6 +586,96 @@ int fmcw_beams_enqueue(fmcw_beams* b, const void* spec_dev, size_t n_frames, flo
  * beams.  0 = the built-in bound (the workgroups resident at once), else min(that bound, grid).
  * Results never depend on it. */
 int fmcw_beams_set_grid_for_test(fmcw_beams* b, uint32_t grid);
+
+/* ---- Cell-averaging CFAR (CA / GO / SO): a detector whose cost does not depend on the data ----
+ * The reference's detectors are the two ordered-statistic CFARs; this is the cell-averaging family
+ * beside them, an object of its own (not part of fmcw_handle / fmcw_config).  It does the same
+ * arithmetic on every cell whatever the map holds, so a caller can budget it, for instance under the
+ * beamformer's n_frames * n_beams maps.  It is not a replacement for OS-CFAR on heavy-tailed clutter.
+ * Everything below is fp32.
+ *
+ * Input.  map[f][r][d] float32, [frame][range][doppler], as fmcw_enqueue and fmcw_beams_enqueue write
+ * it.  Cells enter as fmcw_cfar takes them: negative cells and -0.0 become +0.  NaN is outside the
+ * specification.  +Inf follows IEEE arithmetic as written.
+ *
+ * Window.  ref_range (Rr), guard_range (Gr), ref_doppler (Rd), guard_doppler (Gd), each named by the
+ * axis it acts on, as the cfar2d_* fields are.  Half extents Hr = Rr + Gr, Hd = Rd + Gd.  Doppler is
+ * circular.  A CUT is tested only when Hr <= r < n_range - Hr; elsewhere there is no detection (the
+ * build's rule for the 2-D OS-CFAR).  Reference set: the (2Hr+1) x (2Hd+1) window minus
+ * the (2Gr+1) x (2Gd+1) guard block; N = (2Hr+1)(2Hd+1) - (2Gr+1)(2Gd+1), 128 with the defaults
+ * 4/1/4/2.
+ *
+ * Canonical sums.  These shared partial sums are the definition: a kernel that computes each once per
+ * cell and shares it between the CUTs that use it is bit-exact by construction.  A sum "in ascending
+ * order" starts from its first term and adds the next terms one at a time; an empty sum is +0.0.
+ * Row-wise, Doppler indices mod n_doppler:
+ *   Lg[r][d] = sum of m[r][d+dd] for dd = -Hd .. -Gd-1, in ascending order,
+ *   Cg[r][d] = the same for dd = -Gd .. Gd,
+ *   Rg[r][d] = the same for dd = Gd+1 .. Hd,
+ *   H[r][d]  = (Lg + Cg) + Rg.
+ * Column-wise, in ascending dr:
+ *   U = sum of H[r+dr][d]  for dr = -Hr .. -Gr-1,     D = the same for dr = Gr+1 .. Hr,
+ *   L = sum of Lg[r+dr][d] for dr = -Gr .. Gr,        R = sum of Rg[r+dr][d] for dr = -Gr .. Gr.
+ * Halves: A = U + L (rows above, left segments), B = D + R (rows below, right segments); N/2 cells
+ * each.
+ *
+ * Threshold, one multiplication:  CA: T = kc * (A + B), kc = (float)((double)alpha / N);
+ * GO: T = kh * max(A, B);  SO: T = kh * min(A, B), kh = (float)((double)alpha / (N/2)).  The
+ * constants are formed once on the host.  There is no division and no multiply-add anywhere, so no
+ * contraction can change a bit.
+ *
+ * Decision and order.  Detect iff m_cut > T (strict).  The record is {frame, range, doppler,
+ * mag = m_cut, threshold = T}.  The list is strictly increasing in (frame, range, doppler), which is
+ * what the plot extractor requires of its input.
+ *
+ * Degenerate windows are allowed and fall out of the same formulas: Rr = 0 is a 1-D CA along Doppler
+ * (U = D = 0), Rd = 0 a 1-D CA along range.
+ *
+ * Validation: each ref in 0..8, each guard in 0..4, N >= 2, 2Hd + 1 <= n_doppler, 2Hr + 1 <= n_range. */
+typedef enum { FMCW_CACFAR_CA = 0, FMCW_CACFAR_GO = 1, FMCW_CACFAR_SO = 2 } fmcw_cacfar_mode;
+typedef struct fmcw_cacfar_config {   /* 12 words, 48 bytes */
+  uint32_t n_range;            /* as fmcw_config: power of two, 64..8192 */
+  uint32_t n_doppler;          /* as fmcw_config: power of two, 32..1024 */
+  int32_t mode;                /* fmcw_cacfar_mode */
+  uint32_t ref_range;          /* Rr, 0..8 */
+  uint32_t guard_range;        /* Gr, 0..4 */
+  uint32_t ref_doppler;        /* Rd, 0..8 */
+  uint32_t guard_doppler;      /* Gd, 0..4 */
+  float alpha;                 /* finite, > 0 */
+  uint32_t max_frames;         /* >= 1; max_frames x n_range x n_doppler < 2^32 */
+                               /* device memory of a detector: 8 B per tile of max_frames (a tile is
+                                  max(64, 65536 / n_doppler) range rows of a frame, or the whole frame
+                                  when n_range is smaller): a count and an offset.  No per-cell
+                                  scratch, so well under 1 bit per cell */
+  int32_t device_id;           /* 0..63 */
+  uint32_t reserved[2];        /* must be 0 */
+} fmcw_cacfar_config;
+typedef struct fmcw_cacfar fmcw_cacfar;
+/* Defaults: 1024, 128, CA, window 4/1/4/2, alpha 4.0, max_frames 1, device 0. */
+void fmcw_cacfar_config_default(fmcw_cacfar_config* cfg);
+/* Validates every field before any device access (FMCW_EINVAL, the message names the field, *out is
+ * NULL), then FMCW_ENODEV / FMCW_ENOMEM as fmcw_beams_create. */
+int fmcw_cacfar_create(const fmcw_cacfar_config* cfg, fmcw_cacfar** out);
+int fmcw_cacfar_destroy(fmcw_cacfar* c);   /* NULL is FMCW_OK */
+/* Device pointers only; stream-ordered, allocates nothing, never synchronises and keeps no state
+ * between calls, so it can be captured into a hipGraph after fmcw_enqueue or fmcw_beams_enqueue on the
+ * same stream and replayed.  One stream at a time per detector (its per-tile words are shared by its
+ * calls).  Three launches: a count pass (per-tile counts, tiles in (frame, range) order), a scan of
+ * the counts, and an emit pass that recomputes and stores at the scanned offsets: two reads of the
+ * map, whatever it holds.
+ * map_dev: n_frames maps, 16-byte aligned; n_frames > max_frames is FMCW_EINVAL.
+ * n_dets_dev: FMCW_STATUS_WORDS words: [0] the detections found (may exceed det_cap: then the first
+ *   det_cap records of the ordered list are written and nothing is stored beyond them), [1..3] 0; so
+ *   fmcw_gather_dets, the plot extractor and the bearing estimator take the list and the words
+ *   unchanged.  The list is complete and ordered at any density.
+ * dets_dev: det_cap records, 16-byte aligned; may be NULL with det_cap = 0, which counts only.
+ * n_frames == 0 writes four zero words and touches no record. */
+int fmcw_cacfar_enqueue(fmcw_cacfar* c, const float* map_dev, size_t n_frames, fmcw_det* dets_dev,
+                        size_t det_cap, uint32_t* n_dets_dev, void* stream);
+/* Test hook: bounds the workgroups of the two persistent passes, which stride over the tiles, so that
+ * a small call drives a workgroup through several tiles and frames.  0 = the built-in bound (the
+ * workgroups resident at once), else min(that bound, grid).  Results never depend on it. */
+int fmcw_cacfar_set_grid_for_test(fmcw_cacfar* c, uint32_t grid);
 
 /* ---- Track-while-scan tracker (host side) ----------------------------------------------
  * Replaces rtl/src/tws_tracker.vhd (radar_core.vhd:424-438): MAX_TRACKS alpha-beta tracks in
