@@ -6,6 +6,8 @@
 // INITIATE :234-263, MAINTAIN :265-271, OUTPUT :273-295).  Serial and data-dependent over at
 // most 64 detections x 32 tracks per scan, so it runs on the CPU after the detection list
 // comes back (or after the RCCL gather): it is the consumer of the GPU path, not part of it.
+// fmcw_tws_dev_* (fmcw_tws_dev.hip) runs the same statements on the device, one wave per track
+// file, for callers whose list stays there; this file is its reference and the default.
 //
 // A scan here is one frame (the reference wiring ends a scan per range row).
 // rtl_compat = 1 reproduces the VHDL bit for bit, including its quirks (field widths that

@@ -8,11 +8,12 @@ from ._lib import FmcwError, load, device_count, LIB_PATH, HEADER_PATH  # noqa: 
 from .radar_core import RadarCore, RadarOutput, DeviceBuffer, DET_DTYPE, magnitude  # noqa: F401
 from .radar_core import pack_adc_words, adc_words_to_cube  # noqa: F401
 from .tracker import TwsTracker, TRACK_DTYPE  # noqa: F401
+from .tracker_dev import DeviceTwsTracker  # noqa: F401
 from .plots import PlotExtractor, PLOT_DTYPE  # noqa: F401
 from .bearings import BearingEstimator, BEARING_DTYPE  # noqa: F401
 from .beams import BeamFormer, steering_weights  # noqa: F401
 from .cacfar import CaCfar  # noqa: F401
 from . import synth, formats  # noqa: F401
 
-__all__ = ["CaCfar", "BeamFormer", "steering_weights", "BearingEstimator", "BEARING_DTYPE", "PlotExtractor", "PLOT_DTYPE", "RadarCore", "RadarOutput", "DeviceBuffer", "DET_DTYPE", "FmcwError", "load",
+__all__ = ["DeviceTwsTracker", "CaCfar", "BeamFormer", "steering_weights", "BearingEstimator", "BEARING_DTYPE", "PlotExtractor", "PLOT_DTYPE", "RadarCore", "RadarOutput", "DeviceBuffer", "DET_DTYPE", "FmcwError", "load",
            "device_count", "magnitude", "TwsTracker", "TRACK_DTYPE", "synth", "formats", "pack_adc_words", "adc_words_to_cube"]

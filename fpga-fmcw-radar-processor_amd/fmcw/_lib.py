@@ -43,6 +43,7 @@ STATUS_WORDS = 4      # FMCW_STATUS_WORDS: n_dets_dev = found, lost, window / wo
 PLOT_STATUS_WORDS = 2  # FMCW_PLOT_STATUS_WORDS: n_plots_dev = plots found, records not examined
 BEARING_STATUS_WORDS = 2  # FMCW_BEARING_STATUS_WORDS: n_out_dev = records processed, out of range
 CACFAR_CA, CACFAR_GO, CACFAR_SO = 0, 1, 2   # fmcw_cacfar_mode
+TWS_DEV_STATUS_WORDS = 2  # FMCW_TWS_DEV_STATUS_WORDS: status_dev = records not examined, out of range
 BEARING_NO_ANGLE, BEARING_ONE_RX, BEARING_OUT_OF_RANGE = 1, 2, 4   # fmcw_bearing.flags bits
 
 STATUS_NAMES = {0: "FMCW_OK", -1: "FMCW_EINVAL", -2: "FMCW_ENOMEM", -3: "FMCW_EHIP",
@@ -114,6 +115,11 @@ class FmcwTwsConfig(C.Structure):
                 ("alpha_q8", C.c_uint32), ("beta_q8", C.c_uint32), ("rtl_compat", C.c_int32)]
 
 
+class FmcwTwsDevConfig(C.Structure):
+    _fields_ = [("tws", FmcwTwsConfig), ("n_streams", C.c_uint32), ("max_scans", C.c_uint32),
+                ("device_id", C.c_int32)]
+
+
 class FmcwTrack(C.Structure):
     _fields_ = [("id", C.c_uint16), ("status", C.c_uint8), ("quality", C.c_uint8),
                 ("range_q2", C.c_int32), ("doppler_q2", C.c_int32), ("vel_r", C.c_int32),
@@ -176,6 +182,12 @@ SIGNATURES = {
     "fmcw_tws_create": (_I, [C.POINTER(FmcwTwsConfig), C.POINTER(_VP)]),
     "fmcw_tws_destroy": (_I, [_VP]),
     "fmcw_tws_scan": (_I, [_VP, _VP, _SZ, C.POINTER(FmcwTrack), _SZ, C.POINTER(_SZ), _U32P]),
+    "fmcw_tws_dev_config_default": (None, [C.POINTER(FmcwTwsDevConfig)]),
+    "fmcw_tws_dev_create": (_I, [C.POINTER(FmcwTwsDevConfig), C.POINTER(_VP)]),
+    "fmcw_tws_dev_destroy": (_I, [_VP]),
+    "fmcw_tws_dev_reset": (_I, [_VP, _VP]),
+    "fmcw_tws_dev_enqueue": (_I, [_VP, _VP, _SZ, _SZ, _VP, _SZ, _VP, _SZ, _VP, _VP, _VP]),
+    "fmcw_tws_dev_set_grid_for_test": (_I, [_VP, C.c_uint32]),
 }
 
 _lib = None

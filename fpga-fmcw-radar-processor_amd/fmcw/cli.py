@@ -17,7 +17,9 @@ Outputs in --out-dir (names the visualizer searches, model/visualize_radar_targe
   --cfar ca|go|so [--ca-alpha 4] detects with the cell-averaging family (fmcw.cacfar: CA, greatest-of,
                  smallest-of; the 2-D window 4/1/4/2) on the map of the path run without a CFAR
   ADR_tracks.txt (with --tracks): the track-while-scan log, one scan per frame
-                 ("TRK id R= D= Q=" / "SCAN_END ACTIVE=n", tb_radar_core.vhd:163-180)
+                 ("TRK id R= D= Q=" / "SCAN_END ACTIVE=n", tb_radar_core.vhd:163-180);
+                 --tracker gpu runs the device tracker (fmcw.tracker_dev) and writes the same file;
+                 with --beams B it tracks the beams' detections, one track file per beam
   ADR_plots.txt (with --plots [--plot-window R D]): one line per plot (local-maximum detection
                  of its R x D window, fmcw.plots): "frame r d mag n_cells r+d_range d+d_doppler";
                  with --plots, --tracks feeds the tracker each frame's plots, not its detections
@@ -44,6 +46,7 @@ from .bearings import BearingEstimator
 from .plots import PlotExtractor
 from .radar_core import DET_DTYPE, DeviceBuffer, RadarCore, adc_words_to_cube
 from .tracker import TwsTracker
+from .tracker_dev import DeviceTwsTracker
 
 
 def load_cube(path: Path, ns: int, nc: int):
@@ -82,6 +85,9 @@ def build_parser():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--tracks", action="store_true", help="run the TWS tracker, write ADR_tracks.txt")
     ap.add_argument("--tracker-rtl", action="store_true", help="tracker in RTL-compat mode")
+    ap.add_argument("--tracker", default="host", choices=["host", "gpu"],
+                    help="with --tracks: the host tracker, one frame at a time (default), or the device "
+                         "tracker over the whole call's list (with --beams B: one track file per beam)")
     ap.add_argument("--plots", action="store_true",
                     help="group the detections into plots (one per local maximum), write ADR_plots.txt; "
                          "--tracks then tracks the plots")
@@ -203,7 +209,20 @@ def main(argv=None):
               f"{a.out_dir / 'ADR_beam_detections.txt'}")
     if spec is not None:
         spec.free()
-    if a.tracks:
+    if a.tracks and a.tracker == "gpu":
+        # the whole call's list through the device tracker; with --beams, one track file per beam
+        # over the beams' detections (frame = f * B + b), grouped into plots first with --plots
+        n_streams, recs = 1, scans
+        if a.beams:
+            n_streams, recs = a.beams, bdets
+            if a.plots:
+                with PlotExtractor(N_RANGE=a.n_range, N_DOPPLER=a.n_doppler, win=tuple(a.plot_window),
+                                   max_dets=max(len(bdets), 1), device=a.device) as px:
+                    recs = px.extract(bdets)
+        with DeviceTwsTracker(n_streams=n_streams, max_scans=nf, device=a.device,
+                              rtl_compat=a.tracker_rtl) as trk:
+            formats.write_tracks(a.out_dir / "ADR_tracks.txt", trk.run(recs, nf))
+    elif a.tracks:
         with TwsTracker(rtl_compat=a.tracker_rtl) as trk:
             hist = []
             for f in range(nf):

@@ -162,13 +162,16 @@ def write_tracks(path, scans) -> None:
     """Track log as rtl/src/tb_radar_core.vhd:163-180 writes it: per scan, one
     'TRK id R=range D=doppler Q=quality' line per reported track (R, D = the Q2 trk_range /
     trk_doppler words as signed integers), then 'SCAN_END ACTIVE=n'.  scans: iterable of
-    (tracks, active) with tracks in fmcw.tracker.TRACK_DTYPE."""
+    (tracks, active) with tracks in fmcw.tracker.TRACK_DTYPE (TwsTracker.scan), or of lists over
+    streams of (tracks, active) (DeviceTwsTracker.run): a scan's streams follow each other, each
+    with its own SCAN_END line, so that one stream writes what the first form writes."""
     with open(path, "w") as f:
-        for tracks, active in scans:
-            for t in tracks:
-                f.write(f"TRK {int(t['id'])} R={int(t['range_q2'])} D={int(t['doppler_q2'])} "
-                        f"Q={int(t['quality'])}\n")
-            f.write(f"SCAN_END ACTIVE={int(active)}\n")
+        for scan in scans:
+            for tracks, active in ([scan] if isinstance(scan, tuple) else scan):
+                for t in tracks:
+                    f.write(f"TRK {int(t['id'])} R={int(t['range_q2'])} D={int(t['doppler_q2'])} "
+                            f"Q={int(t['quality'])}\n")
+                f.write(f"SCAN_END ACTIVE={int(active)}\n")
 
 
 def read_tracks(path):

@@ -92,7 +92,10 @@ extern "C" {
                                functions and types of its own, nothing existing changes.
                                Still 8 with the cell-averaging detector (fmcw_cacfar_*,
                                fmcw_cacfar_config): functions and types of its own, nothing
-                               existing changes */
+                               existing changes.
+                               Still 8 with the device tracker (fmcw_tws_dev_*, fmcw_tws_dev_config):
+                               functions and types of its own; the host tracker fmcw_tws_* and every
+                               existing struct, enum and signature are unchanged */
 
 typedef enum {
   FMCW_OK = 0,
@@ -680,7 +683,8 @@ int fmcw_cacfar_set_grid_for_test(fmcw_cacfar* c, uint32_t grid);
 /* ---- Track-while-scan tracker (host side) ----------------------------------------------
  * Replaces rtl/src/tws_tracker.vhd (radar_core.vhd:424-438): MAX_TRACKS alpha-beta tracks in
  * Q2 bins with Q8 gains over the detection list, one scan (= one frame's detections) per
- * fmcw_tws_scan.  CPU code: serial, <= 64 detections x 64 tracks per scan.
+ * fmcw_tws_scan.  CPU code: serial, <= 64 detections x 64 tracks per scan.  The same tracker over a
+ * device-resident list, many scans and independent track files per call, is fmcw_tws_dev_* below.
  * rtl_compat = 1 is the VHDL bit for bit (wrapping field widths, the signal read of
  * best_distance in ASSOCIATE, the 6-bit detection counter); 0 is the intended tracker (wide
  * integers, nearest-neighbour association).  Output: firm and coasting tracks in track-file
@@ -713,6 +717,77 @@ int fmcw_tws_create(const fmcw_tws_config* cfg, fmcw_tws** out);
 int fmcw_tws_destroy(fmcw_tws* t);
 int fmcw_tws_scan(fmcw_tws* t, const fmcw_det* dets, size_t n_dets, fmcw_track* out, size_t cap,
                   size_t* n_out, uint32_t* n_active);
+
+/* ---- Track-while-scan tracker (device side) --------------------------------------------
+ * fmcw_tws_scan on the GPU, over a record list that is already there: the list and count word that
+ * fmcw_enqueue, fmcw_cfar, fmcw_cacfar_enqueue or fmcw_plots_enqueue wrote go in as they are, so a
+ * caller who wants tracks no longer synchronises, copies the list back and slices it by frame, and
+ * the whole chain can be captured into one hipGraph.  An object of its own, not part of fmcw_handle.
+ * The host tracker above stays the default and is the second reference of this one's tests.
+ *
+ * Records begin with {uint32 frame; uint16 range; uint16 doppler; float mag}: rec_stride is 16
+ * (fmcw_det) or 32 (fmcw_plot).  .frame must be non-decreasing along the list (those four producers
+ * guarantee it).  The kernels examine n = min(n_recs_dev[0], rec_cap) records; n is read on the device.
+ *
+ * Scans and streams.  A tracker holds n_streams independent track files.  Record frame m belongs to
+ * scan m / n_streams of stream m % n_streams, which is the beamformer's frame = f * n_beams + b; with
+ * n_streams = 1 a frame is a scan.  A call runs scans 0 .. n_scans-1 of every stream in order; a
+ * (scan, stream) without records is still a scan (its tracks coast), as fmcw_tws_scan with n_dets = 0.
+ *
+ * Per scan: the detections are the scan's records in list order (the first max_dets are kept), and
+ * everything else is fmcw_tws_scan statement for statement for both rtl_compat values: the magnitude
+ * rounding (<= 0 gives 0, >= 4e9 all ones, else (uint64)(m + 0.5f); a NaN magnitude is outside the
+ * specification), the RTL's wrapping widths, RESIZE and 6-bit detection counter, the best_distance /
+ * best_idx signal carried from one active track to the next, from scan to scan and from call to call
+ * (kept per stream, with the power-up value), nearest-neighbour association with the lowest index
+ * winning ties in the intended mode, INITIATE in detection order into the lowest free slot.  Integers
+ * are 64-bit on the device as on the host.
+ *
+ * State is device-resident and persists between calls: two calls of 8 scans equal one call of 16.  A
+ * captured graph that is replayed therefore ADVANCES the track files on every replay (a replay is
+ * another n_scans scans, not a repetition of the same ones); fmcw_tws_dev_reset, itself capturable,
+ * puts every track file back to power-up.  One stream at a time per tracker.
+ *
+ * Output, fixed stride, no compaction.  With m = scan * n_streams + stream:
+ *   tracks_dev[m * track_cap + j], j < min(n_out, track_cap): the firm and coasting tracks in
+ *     track-file order (the records fmcw_tws_scan returns for that scan); slots beyond are untouched;
+ *   counts_dev[2 m] = n_out (may exceed track_cap), counts_dev[2 m + 1] = n_active.
+ *   status_dev[0] = n_recs_dev[0] - n, the records not examined;
+ *   status_dev[1] = examined records whose frame is >= n_scans * n_streams: ignored, and no memory is
+ *     indexed by them.
+ * The last kernel of every call that returns FMCW_OK writes the status words.  n_scans = 0 writes only
+ * them.  Two launches: a frame index over the list (4 B per (scan, stream) of scratch, allocated at
+ * create for max_scans), then one wave64 per stream, serial over its scans. */
+typedef struct fmcw_tws_dev_config {   /* 12 words, 48 bytes */
+  fmcw_tws_config tws;     /* same fields, same limits as fmcw_tws_create */
+  uint32_t n_streams;      /* independent track files, 1..4096 */
+  uint32_t max_scans;      /* most scans one call runs, >= 1 (max_scans x n_streams < 2^31); sizes the
+                              frame index scratch */
+  int32_t device_id;       /* 0..63 */
+} fmcw_tws_dev_config;
+typedef struct fmcw_tws_dev fmcw_tws_dev;
+#define FMCW_TWS_DEV_STATUS_WORDS 2
+/* Defaults: fmcw_tws_config_default, 1 stream, 1024 scans, device 0. */
+void fmcw_tws_dev_config_default(fmcw_tws_dev_config* cfg);
+/* Validates every field before any device access (FMCW_EINVAL, the message names the field, *out is
+ * NULL), then FMCW_ENODEV / FMCW_ENOMEM as fmcw_plots_create.  Device memory: 3840 B per stream and
+ * 4 B per (scan, stream) of max_scans.  The track files are at power-up when it returns. */
+int fmcw_tws_dev_create(const fmcw_tws_dev_config* cfg, fmcw_tws_dev** out);
+int fmcw_tws_dev_destroy(fmcw_tws_dev* t);   /* NULL is FMCW_OK */
+/* Stream-ordered: every track file back to power-up (no track, best_distance all ones). */
+int fmcw_tws_dev_reset(fmcw_tws_dev* t, void* stream);
+/* Device pointers only; stream-ordered, allocates nothing, never synchronises.  Arguments are checked
+ * before any device access: rec_stride 16 or 32, track_cap >= 1, n_scans <= max_scans, no NULL
+ * (recs_dev may be NULL with rec_cap = 0; tracks_dev and counts_dev with n_scans = 0).
+ * tracks_dev: n_scans x n_streams x track_cap records; counts_dev: 2 x n_scans x n_streams words;
+ * status_dev: FMCW_TWS_DEV_STATUS_WORDS words. */
+int fmcw_tws_dev_enqueue(fmcw_tws_dev* t, const void* recs_dev, size_t rec_stride, size_t rec_cap,
+                         const uint32_t* n_recs_dev, size_t n_scans, fmcw_track* tracks_dev,
+                         size_t track_cap, uint32_t* counts_dev, uint32_t* status_dev, void* stream);
+/* Test hook: bounds the workgroups of both kernels (0 = the built-in bound, else the minimum), so that a
+ * short list drives one workgroup of the index kernel through several 1024-record tiles and one wave
+ * of the tracker through several streams.  Results never depend on it. */
+int fmcw_tws_dev_set_grid_for_test(fmcw_tws_dev* t, uint32_t grid);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
