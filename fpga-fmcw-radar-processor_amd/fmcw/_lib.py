@@ -109,6 +109,13 @@ class FmcwCaCfarConfig(C.Structure):
                 ("device_id", C.c_int32), ("reserved", C.c_uint32 * 2)]
 
 
+class FmcwCmapConfig(C.Structure):
+    _fields_ = [("n_range", C.c_uint32), ("n_doppler", C.c_uint32), ("n_streams", C.c_uint32),
+                ("gain", C.c_float), ("alpha", C.c_float), ("floor", C.c_float), ("clip", C.c_float),
+                ("spread_range", C.c_uint32), ("spread_doppler", C.c_uint32), ("warmup", C.c_uint32),
+                ("max_frames", C.c_uint32), ("device_id", C.c_int32), ("reserved", C.c_uint32 * 4)]
+
+
 class FmcwTwsConfig(C.Structure):
     _fields_ = [("max_tracks", C.c_uint32), ("max_dets", C.c_uint32), ("init_hits", C.c_uint32),
                 ("coast_max", C.c_uint32), ("gate_r", C.c_uint32), ("gate_d", C.c_uint32),
@@ -178,6 +185,14 @@ SIGNATURES = {
     "fmcw_cacfar_destroy": (_I, [_VP]),
     "fmcw_cacfar_enqueue": (_I, [_VP, _VP, _SZ, _VP, _SZ, _VP, _VP]),
     "fmcw_cacfar_set_grid_for_test": (_I, [_VP, C.c_uint32]),
+    "fmcw_cmap_config_default": (None, [C.POINTER(FmcwCmapConfig)]),
+    "fmcw_cmap_create": (_I, [C.POINTER(FmcwCmapConfig), C.POINTER(_VP)]),
+    "fmcw_cmap_destroy": (_I, [_VP]),
+    "fmcw_cmap_enqueue": (_I, [_VP, _VP, _SZ, _VP, _SZ, _VP, _VP]),
+    "fmcw_cmap_reset": (_I, [_VP, _VP]),
+    "fmcw_cmap_get_state": (_I, [_VP, _VP, _VP, _VP]),
+    "fmcw_cmap_set_state": (_I, [_VP, _VP, _VP, _VP]),
+    "fmcw_cmap_set_grid_for_test": (_I, [_VP, C.c_uint32]),
     "fmcw_tws_config_default": (None, [C.POINTER(FmcwTwsConfig)]),
     "fmcw_tws_create": (_I, [C.POINTER(FmcwTwsConfig), C.POINTER(_VP)]),
     "fmcw_tws_destroy": (_I, [_VP]),

@@ -95,7 +95,9 @@ extern "C" {
                                existing changes.
                                Still 8 with the device tracker (fmcw_tws_dev_*, fmcw_tws_dev_config):
                                functions and types of its own; the host tracker fmcw_tws_* and every
-                               existing struct, enum and signature are unchanged */
+                               existing struct, enum and signature are unchanged.
+                               Still 8 with the clutter map (fmcw_cmap_*, fmcw_cmap_config): functions
+                               and types of its own, nothing existing changes */
 
 typedef enum {
   FMCW_OK = 0,
@@ -679,6 +681,107 @@ int fmcw_cacfar_enqueue(fmcw_cacfar* c, const float* map_dev, size_t n_frames, f
  * a small call drives a workgroup through several tiles and frames.  0 = the built-in bound (the
  * workgroups resident at once), else min(that bound, grid).  Results never depend on it. */
 int fmcw_cacfar_set_grid_for_test(fmcw_cacfar* c, uint32_t grid);
+
+/* ---- Clutter map (Nitzberg's clutter-map CFAR): a threshold per cell from the cell's own history ----
+ * Every detector above estimates its threshold from a cell's spatial neighbours within one frame, which
+ * goes wrong at a clutter edge (the window straddles two levels) and in range-dependent clutter.  The
+ * clutter map looks at the same cell in earlier scans instead: a per-cell exponential average over scans,
+ * and a cell is detected when it exceeds a multiple of its own history.  An object of its own (not part
+ * of fmcw_handle / fmcw_config), and the first stage whose state is a function of the maps and lives on
+ * the device between calls.  Everything below is fp32, and every operation is rounded on its own: there
+ * is no multiply-add, so no contraction can change a bit.
+ *
+ * Streams.  n_streams (B) independent maps, one per beam or sensor.  Frame f of a call belongs to stream
+ * f % B, the order in which fmcw_beams_enqueue writes its n_frames * n_beams maps; a call's n_frames is
+ * a multiple of B, and its n_frames / B scans of a stream are taken in frame order.
+ *
+ * State, device memory owned by the object, persistent between calls.  Per stream a plane c[r][d] of
+ * float32 and an age word (uint32, the scans taken since the last reset, saturating at 0xFFFFFFFF).
+ * Create and fmcw_cmap_reset set every age to 0; the planes' contents are then irrelevant.
+ *
+ * One scan of stream b, map m, age a.  Per cell (r, d):
+ *   x = m > 0 ? m : +0        negative cells and -0.0 become +0, as for fmcw_cfar and the
+ *                             cell-averaging detector; NaN and Inf are outside the specification.
+ *   a == 0:  c' = x, and no cell is tested.
+ *   a >= 1:  every term uses the state from before this scan's update:
+ *     M  = the maximum of c[r+dr][(d+dd) mod n_doppler] over dr = -Sr .. Sr, dd = -Sd .. Sd
+ *          (spread_range Sr, spread_doppler Sd), rows 0 <= r+dr < n_range only: range is clipped, Doppler
+ *          is circular.  A maximum is exact in any order.
+ *     T  = fmaxf(alpha * M, floor)
+ *     detect iff a >= warmup and x > T (strict); the record is {frame, range, doppler, mag = x,
+ *          threshold = T}, frame being the frame's index within the call.
+ *     u  = x when clip == 0, else fminf(x, fmaxf(clip * c, floor)), c being the cell's own value: this
+ *          limits how fast a target burns into the map.
+ *     t  = u - c;  p = gain * t;  c' = c + p      three operations, three roundings.
+ *   After the scan: a' = min(a + 1, 0xFFFFFFFF).
+ * The update is unconditional: it does not depend on the decision.  A cell's recurrence then depends only
+ * on the cell's own history (x and c), never on a neighbour's, so a workgroup can recompute the
+ * recurrence of the halo rows it needs for M without exchanging anything with its neighbours, and the
+ * state does not depend on det_cap.  A persistent target therefore raises its own threshold; clip bounds
+ * the rate.
+ *
+ * Order.  The list is strictly increasing in (frame, range, doppler), which is what the plot extractor
+ * requires of its input.  Every row is tested: there is no excluded border.
+ *
+ * Planes given to fmcw_cmap_set_state hold finite values >= +0 (what a scan leaves behind); anything else
+ * is outside the specification. */
+typedef struct fmcw_cmap_config {   /* 16 words, 64 bytes */
+  uint32_t n_range;            /* as fmcw_config: power of two, 64..8192 */
+  uint32_t n_doppler;          /* as fmcw_config: power of two, 32..1024 */
+  uint32_t n_streams;          /* B, 1..64 */
+  float gain;                  /* g: finite, 0 < g <= 1 */
+  float alpha;                 /* finite, > 0 */
+  float floor;                 /* finite, >= 0: the least threshold, and the least clip level */
+  float clip;                  /* 0 (off), or finite and >= 1 */
+  uint32_t spread_range;       /* Sr, 0..4 */
+  uint32_t spread_doppler;     /* Sd, 0..4; 2 Sd + 1 <= n_doppler */
+  uint32_t warmup;             /* >= 1: no detection while a stream's age is below it */
+  uint32_t max_frames;         /* a multiple of B, >= B; max_frames x n_range x n_doppler < 2^32 */
+                               /* device memory of a map: two copies of the B planes (a call reads one
+                                  and writes the other, so that a workgroup never reads a halo row its
+                                  neighbour has already written), 8 B per tile of max_frames (a tile is
+                                  8192 / n_doppler range rows of a frame, or the whole frame when
+                                  n_range is smaller), and 8 B per stream */
+  int32_t device_id;           /* 0..63 */
+  uint32_t reserved[4];        /* must be 0 */
+} fmcw_cmap_config;
+typedef struct fmcw_cmap fmcw_cmap;
+/* Defaults: 1024, 128, 1 stream, gain 0.125, alpha 4.0, floor 0, clip 0, spread 1/1, warmup 8,
+ * max_frames 1, device 0. */
+void fmcw_cmap_config_default(fmcw_cmap_config* cfg);
+/* Validates every field before any device access (FMCW_EINVAL, the message names the field, *out is
+ * NULL), then FMCW_ENODEV / FMCW_ENOMEM as fmcw_cacfar_create.  Every age starts at 0. */
+int fmcw_cmap_create(const fmcw_cmap_config* cfg, fmcw_cmap** out);
+int fmcw_cmap_destroy(fmcw_cmap* c);   /* NULL is FMCW_OK */
+/* Device pointers only; stream-ordered, allocates nothing and never synchronises; the ages are read on
+ * the device, never on the host.  It can therefore be captured into a hipGraph after fmcw_enqueue or
+ * fmcw_beams_enqueue on the same stream; the state advances by the call's scans at every replay.  One
+ * stream at a time per map.  Three launches whatever n_frames is: a count pass over (stream, tile) units
+ * that runs all of the call's scans for its tile and leaves the state alone, a scan of the per-(frame,
+ * tile) counts, and an emit pass that repeats the arithmetic, stores the records and writes the state.
+ * map_dev: n_frames maps, 16-byte aligned; n_frames > max_frames, or not a multiple of n_streams, is
+ *   FMCW_EINVAL.
+ * n_dets_dev: FMCW_STATUS_WORDS words: [0] the detections found (may exceed det_cap: then the first
+ *   det_cap records of the ordered list are written and nothing is stored beyond them), [1..3] 0.
+ * dets_dev: det_cap records, 16-byte aligned; may be NULL with det_cap = 0.  The state advances by the
+ *   call's scans whatever det_cap is.
+ * n_frames == 0 writes four zero words and leaves the state alone. */
+int fmcw_cmap_enqueue(fmcw_cmap* c, const float* map_dev, size_t n_frames, fmcw_det* dets_dev, size_t det_cap,
+                      uint32_t* n_dets_dev, void* stream);
+/* Every age goes to 0, in stream order. */
+int fmcw_cmap_reset(fmcw_cmap* c, void* stream);
+/* Stream-ordered copies of the state, for checkpoints and tests: planes_dev holds n_streams planes
+ * [stream][range][doppler] (16-byte aligned), ages_dev n_streams words (4-byte aligned).
+ * fmcw_cmap_get_state: either pointer may be NULL (that part is not copied), not both.
+ * fmcw_cmap_set_state: planes_dev is required; ages_dev may be NULL, which keeps the ages.  A NULL
+ * planes_dev is FMCW_EINVAL: ages without the planes they describe would make the next scan test against
+ * whatever the planes held. */
+int fmcw_cmap_get_state(fmcw_cmap* c, float* planes_dev, uint32_t* ages_dev, void* stream);
+int fmcw_cmap_set_state(fmcw_cmap* c, const float* planes_dev, const uint32_t* ages_dev, void* stream);
+/* Test hook: bounds the workgroups of the two persistent passes, which stride over the (stream, tile)
+ * units.  0 = the built-in bound (the workgroups resident at once), else min(that bound, grid).  Results
+ * never depend on it. */
+int fmcw_cmap_set_grid_for_test(fmcw_cmap* c, uint32_t grid);
 
 /* ---- Track-while-scan tracker (host side) ----------------------------------------------
  * Replaces rtl/src/tws_tracker.vhd (radar_core.vhd:424-438): MAX_TRACKS alpha-beta tracks in
