@@ -1,0 +1,206 @@
+// fmcw_adapt.hip -- adaptive beam weights of include/fmcw.h: the corner-turned spectrum of
+// fmcw_range_ct in, the minimum-variance (MVDR) weight matrix for fmcw_beams_set_weights_dev out.
+//
+// The reference is a single-channel core and has no such stage.  The beamformer applies whatever
+// matrix its caller computed; this object computes one from the data: the sample covariance of the
+// channels over a training window (adapt_kernel.hpp's k_adapt_acc: a real Gram matrix on the f32
+// matrix cores, one partial tile per unit, no atomics) and the diagonally loaded solve under a
+// unit-gain constraint per look direction (k_adapt_fold and k_adapt_solve: the units' tiles summed
+// in a fixed order and the solve in one workgroup, fp64).  Three launches per call; every scratch
+// word a launch reads is written by the one before it in the same call.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "adapt_kernel.hpp"
+#include "internal.hpp"
+
+using fmcw::fail;
+
+static_assert(sizeof(fmcw_adapt_config) == 40, "fmcw.h adaptive-weights layout");
+static_assert(FMCW_ADAPT_INFO_WORDS == 8, "k_adapt_solve writes 8 status words");
+
+namespace {
+
+using AccFn = void (*)(const float2*, fmcw::AdaptGeom, float*);
+
+template <int ROWS>
+AccFn pick_mti(int mti) {
+  return mti == FMCW_MTI_OFF      ? fmcw::k_adapt_acc<ROWS, FMCW_MTI_OFF>
+         : mti == FMCW_MTI_2PULSE ? fmcw::k_adapt_acc<ROWS, FMCW_MTI_2PULSE>
+                                  : fmcw::k_adapt_acc<ROWS, FMCW_MTI_3PULSE>;
+}
+
+bool pow2(uint32_t x) { return x && !(x & (x - 1)); }
+
+int validate(const fmcw_adapt_config& c) {
+  if (!pow2(c.n_range) || c.n_range < 64 || c.n_range > 8192)
+    return fail(FMCW_EINVAL, "n_range=%u: must be a power of two in [64, 8192]", c.n_range);
+  if (!pow2(c.n_doppler) || c.n_doppler < 32 || c.n_doppler > 1024)
+    return fail(FMCW_EINVAL, "n_doppler=%u: must be a power of two in [32, 1024]", c.n_doppler);
+  if (c.n_rx < 1 || c.n_rx > 16) return fail(FMCW_EINVAL, "n_rx=%u: must be in [1, 16] (17..64 is not built)", c.n_rx);
+  if (c.n_beams < 1 || c.n_beams > 64) return fail(FMCW_EINVAL, "n_beams=%u: must be in [1, 64]", c.n_beams);
+  if (c.mti_mode != FMCW_MTI_OFF && c.mti_mode != FMCW_MTI_2PULSE && c.mti_mode != FMCW_MTI_3PULSE)
+    return fail(FMCW_EINVAL, "mti_mode %d (0, 2, 3)", c.mti_mode);
+  if (c.train_rows < 1 || c.train_rows > c.n_range)
+    return fail(FMCW_EINVAL, "train_rows=%u: must be in [1, n_range = %u]", c.train_rows, c.n_range);
+  if (c.train_r0 > c.n_range - c.train_rows)
+    return fail(FMCW_EINVAL, "train_r0=%u: rows [%u, %u) leave the map of n_range = %u", c.train_r0, c.train_r0,
+                c.train_r0 + c.train_rows, c.n_range);
+  if (!std::isfinite(c.loading) || c.loading < 0.f)
+    return fail(FMCW_EINVAL, "loading %g: must be finite and >= 0", (double)c.loading);
+  if (c.reserved != 0) return fail(FMCW_EINVAL, "reserved %u: must be 0", c.reserved);
+  if (c.device_id < 0 || c.device_id > 63) return fail(FMCW_EINVAL, "device_id %d (0..63)", c.device_id);
+  return FMCW_OK;
+}
+
+}  // namespace
+
+struct fmcw_adapt {
+  fmcw_adapt_config cfg;
+  AccFn acc = nullptr;
+  uint32_t rows = 32;      // the accumulator tile: 16 real rows for n_rx <= 8, else 32
+  uint32_t max_grid = 1;   // workgroups of k_adapt_acc that can hold every unit
+  uint32_t grid = 1;       // workgroups at most (fmcw_adapt_set_grid_for_test)
+  float2* a = nullptr;     // the constraint matrix [beam][rx]
+  float* part = nullptr;   // kAdaptMaxUnits partial tiles of rows x rows floats
+  double* part2 = nullptr; // kAdaptFoldParts tiles of rows x rows doubles
+};
+
+extern "C" {
+
+void fmcw_adapt_config_default(fmcw_adapt_config* cfg) {
+  if (!cfg) return;
+  cfg->n_range = 1024;
+  cfg->n_doppler = 128;
+  cfg->n_rx = 1;
+  cfg->n_beams = 1;
+  cfg->mti_mode = FMCW_MTI_OFF;
+  cfg->train_r0 = 0;
+  cfg->train_rows = 1024;
+  cfg->loading = 1e-2f;
+  cfg->reserved = 0;
+  cfg->device_id = 0;
+}
+
+int fmcw_adapt_create(const fmcw_adapt_config* cfg, const float* a_host, fmcw_adapt** out) {
+  if (!cfg || !out) return fail(FMCW_EINVAL, "null argument");
+  *out = nullptr;
+  const int rc = validate(*cfg);
+  if (rc) return rc;
+  if (!a_host) return fail(FMCW_EINVAL, "null a_host");
+  for (uint32_t b = 0; b < cfg->n_beams; ++b) {
+    bool any = false;
+    for (uint32_t k = 0; k < cfg->n_rx; ++k)
+      for (int h = 0; h < 2; ++h) {
+        const float v = a_host[2 * ((size_t)b * cfg->n_rx + k) + h];
+        if (!std::isfinite(v)) return fail(FMCW_EINVAL, "a_host: beam %u, rx %u is not finite", b, k);
+        any = any || v != 0.f;
+      }
+    if (!any) return fail(FMCW_EINVAL, "a_host: beam %u is all zero (no look direction to hold at unit gain)", b);
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
+    (void)hipGetLastError();
+    return fail(FMCW_ENODEV, "no HIP device");
+  }
+  if (cfg->device_id >= ndev) return fail(FMCW_ENODEV, "device_id %d out of range", cfg->device_id);
+  hipDeviceProp_t prop;
+  if (hipSetDevice(cfg->device_id) != hipSuccess || hipGetDeviceProperties(&prop, cfg->device_id) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(FMCW_ENODEV, "device_id %d", cfg->device_id);
+  }
+  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return fail(FMCW_ENODEV, "device %d is %s; this build targets gfx950 (MI355X)", cfg->device_id, prop.gcnArchName);
+  fmcw_adapt* a = new fmcw_adapt();
+  a->cfg = *cfg;
+  a->rows = cfg->n_rx <= 8 ? 16 : 32;
+  a->acc = a->rows == 16 ? pick_mti<16>(cfg->mti_mode) : pick_mti<32>(cfg->mti_mode);
+  a->max_grid = a->grid = fmcw::kAdaptMaxUnits / fmcw::kAdaptWaves;
+  const size_t na = (size_t)cfg->n_beams * cfg->n_rx;
+  const size_t n_part = (size_t)fmcw::kAdaptMaxUnits * a->rows * a->rows;
+  if (hipMalloc(reinterpret_cast<void**>(&a->a), na * sizeof(float2)) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void**>(&a->part), n_part * sizeof(float)) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void**>(&a->part2),
+                (size_t)fmcw::kAdaptFoldParts * a->rows * a->rows * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    fmcw_adapt_destroy(a);
+    return fail(FMCW_ENOMEM, "hipMalloc for the constraint matrix (%zu) and the partial tiles (%zu floats) failed", na,
+                n_part);
+  }
+  if (hipMemcpy(a->a, a_host, na * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    fmcw_adapt_destroy(a);
+    return fail(FMCW_EHIP, "upload of the constraint matrix failed");
+  }
+  *out = a;
+  return FMCW_OK;
+}
+
+int fmcw_adapt_destroy(fmcw_adapt* a) {
+  if (!a) return FMCW_OK;
+  hipSetDevice(a->cfg.device_id);
+  if (a->a) hipFree(a->a);
+  if (a->part) hipFree(a->part);
+  if (a->part2) hipFree(a->part2);
+  delete a;
+  return FMCW_OK;
+}
+
+int fmcw_adapt_set_grid_for_test(fmcw_adapt* a, uint32_t grid) {
+  if (!a) return fail(FMCW_EINVAL, "null adaptive-weights object");
+  a->grid = grid ? std::min(a->max_grid, grid) : a->max_grid;
+  return FMCW_OK;
+}
+
+int fmcw_adapt_enqueue(fmcw_adapt* a, const void* spec_dev, size_t n_frames, void* w_dev, void* cov_dev,
+                       uint32_t* info_dev, void* stream) {
+  if (!a) return fail(FMCW_EINVAL, "null adaptive-weights object");
+  if (n_frames == 0) return FMCW_OK;
+  if (!spec_dev || !w_dev || !info_dev)
+    return fail(FMCW_EINVAL, "null spec_dev, w_dev or info_dev with n_frames %zu", n_frames);
+  if (reinterpret_cast<uintptr_t>(spec_dev) & 7u) return fail(FMCW_EINVAL, "spec_dev must be 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(w_dev) & 7u) return fail(FMCW_EINVAL, "w_dev must be 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(cov_dev) & 15u) return fail(FMCW_EINVAL, "cov_dev must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(info_dev) & 3u) return fail(FMCW_EINVAL, "info_dev must be 4-byte aligned");
+  const fmcw_adapt_config& c = a->cfg;
+  fmcw::AdaptGeom g;
+  g.nd = c.n_doppler;
+  g.nrx = c.n_rx;
+  g.cf = c.train_rows * c.n_doppler;
+  g.spf = (g.cf + 63u) / 64u;
+  if (n_frames > 0x7fffffffu / g.spf)
+    return fail(FMCW_EINVAL, "n_frames %zu: more than 2^31 - 1 steps of 64 training cells (%u per frame)", n_frames,
+                g.spf);
+  g.n_steps = (uint32_t)n_frames * g.spf;
+  g.n_units = std::min(g.n_steps, (uint32_t)fmcw::kAdaptMaxUnits);
+  g.off0 = c.train_r0 * c.n_doppler;
+  g.rx_step = c.n_range * c.n_doppler;
+  if (hipSetDevice(c.device_id) != hipSuccess) return fail(FMCW_EHIP, "hipSetDevice");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const uint32_t n_wg = std::min((g.n_units + fmcw::kAdaptWaves - 1) / fmcw::kAdaptWaves, a->grid);
+  hipLaunchKernelGGL(a->acc, dim3(n_wg), dim3(fmcw::kAdaptThreads), 0, s, static_cast<const float2*>(spec_dev), g,
+                     a->part);
+  if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_adapt_acc launch");
+  const uint32_t n_parts = std::min(g.n_units, (uint32_t)fmcw::kAdaptFoldParts);
+  hipLaunchKernelGGL(fmcw::k_adapt_fold, dim3(n_parts), dim3(256), 0, s, static_cast<const float*>(a->part), g.n_units,
+                     n_parts, a->rows * a->rows, a->part2);
+  if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_adapt_fold launch");
+  fmcw::SolveArgs p;
+  p.nrx = c.n_rx;
+  p.nb = c.n_beams;
+  p.rows = a->rows;
+  p.n_units = g.n_units;
+  p.n_parts = n_parts;
+  p.K = (uint64_t)n_frames * g.cf;
+  p.loading = (double)c.loading;
+  hipLaunchKernelGGL(fmcw::k_adapt_solve, dim3(1), dim3(fmcw::kSolveThreads), 0, s,
+                     static_cast<const double*>(a->part2), static_cast<const float2*>(a->a), p,
+                     static_cast<float2*>(w_dev), static_cast<double2*>(cov_dev), info_dev);
+  if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_adapt_solve launch");
+  return FMCW_OK;
+}
+
+}  // extern "C"

@@ -158,6 +158,16 @@ int fmcw_beams_set_grid_for_test(fmcw_beams* b, uint32_t grid) {
   return FMCW_OK;
 }
 
+int fmcw_beams_set_weights_dev(fmcw_beams* b, const void* w_dev, void* stream) {
+  if (!b) return fail(FMCW_EINVAL, "null beamformer");
+  if (!w_dev) return fail(FMCW_EINVAL, "null w_dev");
+  if (reinterpret_cast<uintptr_t>(w_dev) & 7u) return fail(FMCW_EINVAL, "w_dev must be 8-byte aligned");
+  if (hipSetDevice(b->cfg.device_id) != hipSuccess) return fail(FMCW_EHIP, "hipSetDevice");
+  HIP_TRY(hipMemcpyAsync(b->w, w_dev, (size_t)b->cfg.n_beams * b->cfg.n_rx * sizeof(float2), hipMemcpyDeviceToDevice,
+                         reinterpret_cast<hipStream_t>(stream)));
+  return FMCW_OK;
+}
+
 int fmcw_beams_enqueue(fmcw_beams* b, const void* spec_dev, size_t n_frames, float* maps_dev, void* stream) {
   if (!b) return fail(FMCW_EINVAL, "null beamformer");
   if (n_frames == 0) return FMCW_OK;

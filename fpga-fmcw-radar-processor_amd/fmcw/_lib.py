@@ -102,6 +102,13 @@ class FmcwBeamsConfig(C.Structure):
                 ("reserved", C.c_uint32), ("device_id", C.c_int32)]
 
 
+class FmcwAdaptConfig(C.Structure):
+    _fields_ = [("n_range", C.c_uint32), ("n_doppler", C.c_uint32), ("n_rx", C.c_uint32),
+                ("n_beams", C.c_uint32), ("mti_mode", C.c_int32), ("train_r0", C.c_uint32),
+                ("train_rows", C.c_uint32), ("loading", C.c_float), ("reserved", C.c_uint32),
+                ("device_id", C.c_int32)]
+
+
 class FmcwCaCfarConfig(C.Structure):
     _fields_ = [("n_range", C.c_uint32), ("n_doppler", C.c_uint32), ("mode", C.c_int32),
                 ("ref_range", C.c_uint32), ("guard_range", C.c_uint32), ("ref_doppler", C.c_uint32),
@@ -180,6 +187,12 @@ SIGNATURES = {
     "fmcw_beams_destroy": (_I, [_VP]),
     "fmcw_beams_enqueue": (_I, [_VP, _VP, _SZ, _VP, _VP]),
     "fmcw_beams_set_grid_for_test": (_I, [_VP, C.c_uint32]),
+    "fmcw_beams_set_weights_dev": (_I, [_VP, _VP, _VP]),
+    "fmcw_adapt_config_default": (None, [C.POINTER(FmcwAdaptConfig)]),
+    "fmcw_adapt_create": (_I, [C.POINTER(FmcwAdaptConfig), _VP, C.POINTER(_VP)]),
+    "fmcw_adapt_destroy": (_I, [_VP]),
+    "fmcw_adapt_enqueue": (_I, [_VP, _VP, _SZ, _VP, _VP, _VP, _VP]),
+    "fmcw_adapt_set_grid_for_test": (_I, [_VP, C.c_uint32]),
     "fmcw_cacfar_config_default": (None, [C.POINTER(FmcwCaCfarConfig)]),
     "fmcw_cacfar_create": (_I, [C.POINTER(FmcwCaCfarConfig), C.POINTER(_VP)]),
     "fmcw_cacfar_destroy": (_I, [_VP]),

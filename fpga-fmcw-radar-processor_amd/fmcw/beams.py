@@ -76,6 +76,14 @@ class BeamFormer:
             return x if isinstance(x, int) or x is None else _ptr(x)[0]
         L.check(self._lib.fmcw_beams_enqueue(self._h, p(spec), n_frames, p(maps), stream or None))
 
+    def set_weights_dev(self, w, stream: int = 0) -> None:
+        """fmcw_beams_set_weights_dev: replace the matrix by n_beams x n_rx complex64 on the device
+        (AdaptiveWeights.enqueue's w), stream-ordered and capturable.  Nothing checks the values:
+        weights that are not finite give maps that are not finite.  `self.weights` keeps the matrix
+        of the constructor."""
+        p = w if isinstance(w, int) else _ptr(w)[0]
+        L.check(self._lib.fmcw_beams_set_weights_dev(self._h, p, stream or None))
+
     def form(self, spec) -> np.ndarray:
         """Synchronous.  spec: range_ct output as a DeviceBuffer / CUDA tensor, or a host complex64
         array [frame][rx][range][chirp].  Returns float32 [frame][beam][range][doppler]."""

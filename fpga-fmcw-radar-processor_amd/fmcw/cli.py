@@ -28,7 +28,9 @@ Outputs in --out-dir (names the visualizer searches, model/visualize_radar_targe
                  step across the receive channels in cycles per element, and nu / spacing)
   ADR_beam_detections.txt (with --beams B [--rx-spacing 0.5]): the channels summed coherently into B
                  beams at nu_b = (b - B/2) / B cycles per element (fmcw.beams), the CFAR run on every
-                 beam's map: "frame beam r d mag threshold nu_b sin_theta_b" per detection
+                 beam's map: "frame beam r d mag threshold nu_b sin_theta_b" per detection;
+                 with --adaptive LOADING the beams' weights are the minimum-variance ones (fmcw.adapt)
+                 trained on the call's own frames over the whole map, for the same look directions
 """
 from __future__ import annotations
 
@@ -40,6 +42,7 @@ import math
 import numpy as np
 
 from . import formats, synth
+from .adapt import AdaptiveWeights, steering_vectors
 from .beams import BeamFormer, steering_weights
 from .cacfar import CaCfar
 from .bearings import BearingEstimator
@@ -104,6 +107,9 @@ def build_parser():
     ap.add_argument("--beams", type=int, default=0, metavar="B",
                     help="sum the receive channels coherently into B beams (1..64) at (b - B/2) / B cycles per "
                          "element, run the CFAR on every beam's map, write ADR_beam_detections.txt")
+    ap.add_argument("--adaptive", type=float, default=None, metavar="LOADING",
+                    help="with --beams: adaptive (MVDR) weights for the same look directions, trained on the "
+                         "call's frames, diagonal loading LOADING (finite, >= 0) of the mean channel power")
     return ap
 
 
@@ -111,15 +117,27 @@ CA_MODES = ("ca", "go", "so")
 
 
 def beam_detections(core_args: dict, spec, nf: int, nrx: int, n_beams: int, window: str, device: int,
-                    ca_alpha: float = 4.0):
+                    ca_alpha: float = 4.0, adaptive: float | None = None):
     """The CFAR of `core_args` over the n_frames * n_beams beamformed maps of the device spectrum
-    `spec`: (detections with frame = f * n_beams + b, the beams' nu)."""
+    `spec`: (detections with frame = f * n_beams + b, the beams' nu).  adaptive: the loading of
+    AdaptiveWeights, whose weights then replace the steering weights before the beams are formed."""
     ns, nc = core_args["N_RANGE"], core_args["N_DOPPLER"]
     nus = (np.arange(n_beams) - n_beams // 2) / n_beams
     n_maps = nf * n_beams
     maps = DeviceBuffer(n_maps * ns * nc * 4, device)
     with BeamFormer(ns, nc, nrx, steering_weights(nrx, nus), window=window, device=device) as bf:
-        bf.enqueue(spec, nf, maps)
+        if adaptive is not None:
+            with AdaptiveWeights(ns, nc, nrx, steering_vectors(nrx, nus), loading=adaptive, device=device) as ad:
+                dw, di = DeviceBuffer(ad.w_bytes(), device), DeviceBuffer(32, device)
+                ad.enqueue(spec, nf, dw, None, di)
+                bf.set_weights_dev(dw)
+                bf.enqueue(spec, nf, maps)
+                if int(di.download(np.uint32, (8,))[2]) & 1:
+                    print("adaptive weights: the covariance could not be factorised, conventional beams used")
+                dw.free()
+                di.free()
+        else:
+            bf.enqueue(spec, nf, maps)
     if core_args["cfar"] in CA_MODES:
         with CaCfar(ns, nc, mode=core_args["cfar"], alpha=ca_alpha, max_frames=n_maps, device=device) as ca:
             dets = ca.detect(maps)
@@ -154,6 +172,10 @@ def main(argv=None):
         ap.error("--beams needs a float window (hamming or none)")
     if a.beams and not 1 <= a.beams <= 64:
         ap.error("--beams must be in 1..64")
+    if a.adaptive is not None and not a.beams:
+        ap.error("--adaptive needs --beams")
+    if a.adaptive is not None and not (math.isfinite(a.adaptive) and a.adaptive >= 0):
+        ap.error("--adaptive LOADING must be finite and >= 0")
     if a.beams and a.cfar == "none":
         ap.error("--beams needs a CFAR (os1d or os2d) to run on the beams' maps")
     if not (math.isfinite(a.ca_alpha) and a.ca_alpha > 0):
@@ -163,6 +185,8 @@ def main(argv=None):
     nf, nrx = cube.shape[0], cube.shape[1]
     if a.beams and nrx < 2:
         ap.error(f"--beams needs multi-rx input ({a.input} has one channel)")
+    if a.adaptive is not None and nrx > 16:
+        ap.error(f"--adaptive takes at most 16 channels ({a.input} has {nrx})")
     spec = None
     with RadarCore(N_RANGE=a.n_range, N_DOPPLER=a.n_doppler, N_RX=nrx, in_dtype=dt,
                    cfar="none" if ca else a.cfar, max_frames=nf, device=a.device, window=a.window) as core:
@@ -202,7 +226,7 @@ def main(argv=None):
         print(f"{len(bearings)} bearings ({nrx} rx, spacing {a.rx_spacing}) -> {a.out_dir / 'ADR_bearings.txt'}")
     if a.beams:
         bdets, nus = beam_detections(dict(N_RANGE=a.n_range, N_DOPPLER=a.n_doppler, cfar=a.cfar, device=a.device),
-                                     spec, nf, nrx, a.beams, a.window, a.device, a.ca_alpha)
+                                     spec, nf, nrx, a.beams, a.window, a.device, a.ca_alpha, a.adaptive)
         formats.write_beam_detections(a.out_dir / "ADR_beam_detections.txt", bdets, nus, spacing=a.rx_spacing,
                                       doppler_centred=a.doppler_centred, n_doppler=a.n_doppler)
         print(f"{len(bdets)} detections in {a.beams} beams ({nrx} rx, spacing {a.rx_spacing}) -> "

@@ -97,7 +97,10 @@ extern "C" {
                                functions and types of its own; the host tracker fmcw_tws_* and every
                                existing struct, enum and signature are unchanged.
                                Still 8 with the clutter map (fmcw_cmap_*, fmcw_cmap_config): functions
-                               and types of its own, nothing existing changes */
+                               and types of its own, nothing existing changes.
+                               Still 8 with the adaptive beam weights (fmcw_adapt_*, fmcw_adapt_config)
+                               and fmcw_beams_set_weights_dev: functions and types of their own; a
+                               beamformer that never calls the new function behaves as before */
 
 typedef enum {
   FMCW_OK = 0,
@@ -591,6 +594,94 @@ int fmcw_beams_enqueue(fmcw_beams* b, const void* spec_dev, size_t n_frames, flo
  * beams.  0 = the built-in bound (the workgroups resident at once), else min(that bound, grid).
  * Results never depend on it. */
 int fmcw_beams_set_grid_for_test(fmcw_beams* b, uint32_t grid);
+/* Replaces the beamformer's matrix by w_dev: n_beams x n_rx complex fp32, [beam][rx] as weights_host,
+ * 8-byte aligned, on the beamformer's device.  A stream-ordered device-to-device copy: capturable into
+ * a hipGraph between fmcw_adapt_enqueue and fmcw_beams_enqueue on the same stream, never synchronises.
+ * There is no finiteness check on the device: weights that are not finite give maps that are not
+ * finite.  A beamformer that never calls this keeps the matrix of fmcw_beams_create. */
+int fmcw_beams_set_weights_dev(fmcw_beams* b, const void* w_dev, void* stream);
+
+/* ---- Adaptive beam weights (MVDR): sample covariance and loaded solve --------------------
+ * The beamformer applies the matrix its caller gives it.  A strong off-axis emitter (a jammer, another
+ * FMCW radar) enters a fixed beam through its sidelobes and raises the floor of every cell; the
+ * detectors' thresholds rise with it.  This object chooses the weights from the data (sample matrix
+ * inversion): the channels' covariance over a training window of fmcw_range_ct's spectrum, its
+ * diagonal loaded, and the minimum-variance weights under a unit-gain constraint per look direction.
+ * An object of its own, not part of fmcw_handle / fmcw_config; the reference has no such stage.
+ *
+ * Snapshots.  z_k[c] is the canceller of mti_mode over x_k[c] = spec[f][k][r][c], as the beamformer
+ * defines it (OFF: x[c]; 2-pulse: x[c] - x[c-1]; 3-pulse: x[c] - 2 x[c-1] + x[c-2]; zero delay line
+ * before chirp 0).  The snapshots are the vectors z = (z_0 .. z_{n_rx-1}) at all (f, r, c) with
+ * f < n_frames of the call, r in [train_r0, train_r0 + train_rows) and every chirp c < n_doppler;
+ * K = n_frames * train_rows * n_doppler is their count.
+ *
+ *   R[i][j]  = (1/K) sum z_i conj(z_j)                         sample covariance, Hermitian
+ *   delta    = loading * Re tr(R) / n_rx,   Rl = R + delta I   diagonal loading
+ *   W[b][k]  = conj((Rl^-1 a_b)[k]) / (a_b^H Rl^-1 a_b)        a_b = a_host[b][:], the look direction
+ *
+ * W is in the beamformer's convention, y = sum_k W[b][k] x_k, so sum_k W[b][k] a_b[k] = 1: a plane
+ * wave with array response a_b passes beam b at unit gain, and the output power from everything else
+ * is the least possible.  R = I gives W[b][k] = conj(a_b[k]) / |a_b|^2, the conventional beam
+ * (fmcw.beams.steering_weights for a_b[k] = exp(2 pi i nu_b k)).
+ *
+ * Fallback.  Rl is factorised as L L^H (Cholesky, fp64).  If a pivot is not greater than
+ * FMCW_ADAPT_PIVOT_MIN times the mean diagonal of Rl (a pivot that is zero, negative or NaN
+ * included), or a beam's weights come out not finite, the call writes the conventional weights
+ * conj(a_b) / |a_b|^2 (for every beam in the first case, for that beam in the second) and sets
+ * FMCW_ADAPT_FALLBACK in the status words.  cov and delta are written either way.
+ *
+ * Precision.  The products z_i conj(z_j) are summed in fp32 on the matrix cores over units of at most
+ * ceil(T / n_units) steps of 64 snapshots (T = n_frames * ceil(train_rows * n_doppler / 64),
+ * n_units = min(T, 2048)), the units' partial sums and everything after them in fp64.  The partition
+ * depends on the shape and n_frames alone: the bytes of W, cov and info depend on spec and the
+ * configuration, never on the grid. */
+#define FMCW_ADAPT_FALLBACK 1u        /* status flag: conventional weights were written */
+#define FMCW_ADAPT_PIVOT_MIN 1e-8     /* least Cholesky pivot, relative to the mean diagonal of Rl */
+/* Status words of fmcw_adapt_enqueue (info_dev):
+ *   [0], [1]  K, low and high word
+ *   [2]       flags (FMCW_ADAPT_FALLBACK)
+ *   [3]       n_units, the partial sums the call formed
+ *   [4], [5]  delta as the bits of an fp64, low and high word
+ *   [6], [7]  written as 0 */
+#define FMCW_ADAPT_INFO_WORDS 8
+typedef struct fmcw_adapt_config {   /* 40 bytes */
+  uint32_t n_range;            /* as fmcw_config: power of two, 64..8192 */
+  uint32_t n_doppler;          /* as fmcw_config: power of two, 32..1024 */
+  uint32_t n_rx;               /* 1..16 (17..64, which the beamformer takes, is not built) */
+  uint32_t n_beams;            /* 1..64 */
+  int32_t mti_mode;            /* fmcw_mti_mode: 0, 2 or 3 */
+  uint32_t train_r0;           /* the training rows [train_r0, train_r0 + train_rows) lie in n_range */
+  uint32_t train_rows;         /* >= 1 */
+  float loading;               /* finite, >= 0 */
+  uint32_t reserved;           /* must be 0 */
+                               /* device memory of an object: the constraint matrix (8 B x n_beams x
+                                  n_rx) and 2048 + 64 partial tiles (2.1 MiB for n_rx <= 8, else 8.5 MiB) */
+  int32_t device_id;           /* 0..63 */
+} fmcw_adapt_config;
+typedef struct fmcw_adapt fmcw_adapt;
+/* Defaults: 1024, 128, 1 rx, 1 beam, MTI off, training rows [0, 1024), loading 1e-2, device 0. */
+void fmcw_adapt_config_default(fmcw_adapt_config* cfg);
+/* a_host: n_beams x n_rx complex fp32, interleaved re, im, row-major [beam][rx]: the array response
+ * of each look direction.  Every component finite and no row all zero.  Validates cfg and a_host
+ * before any device access (FMCW_EINVAL, the message names the field), then FMCW_ENODEV /
+ * FMCW_ENOMEM as fmcw_beams_create. */
+int fmcw_adapt_create(const fmcw_adapt_config* cfg, const float* a_host, fmcw_adapt** out);
+int fmcw_adapt_destroy(fmcw_adapt* a);   /* NULL is FMCW_OK */
+/* Device pointers only; stream-ordered, allocates nothing and never synchronises.  Every scratch word
+ * it reads is written earlier in the same call and nothing is zeroed between calls, so it can be
+ * captured into a hipGraph after fmcw_range_ct on the same stream and replayed.  One stream at a time
+ * per object.
+ * spec_dev: n_frames frames as fmcw_range_ct writes them for (n_range, n_doppler, n_rx), 8-byte aligned.
+ * w_dev:    W, n_beams x n_rx complex fp32 [beam][rx], 8-byte aligned: fmcw_beams_set_weights_dev's input.
+ * cov_dev:  R, n_rx x n_rx complex fp64 row-major, 16-byte aligned; NULL: not written.
+ * info_dev: FMCW_ADAPT_INFO_WORDS words (above).
+ * Nothing is stored beyond them.  n_frames == 0 is FMCW_OK and launches nothing. */
+int fmcw_adapt_enqueue(fmcw_adapt* a, const void* spec_dev, size_t n_frames, void* w_dev, void* cov_dev,
+                       uint32_t* info_dev, void* stream);
+/* Test hook: bounds the workgroups of the accumulation kernel, whose waves stride over the units, so
+ * that a small call drives a wave through several units.  0 = the built-in bound (512), else
+ * min(that bound, grid).  Results never depend on it. */
+int fmcw_adapt_set_grid_for_test(fmcw_adapt* a, uint32_t grid);
 
 /* ---- Cell-averaging CFAR (CA / GO / SO): a detector whose cost does not depend on the data ----
  * The reference's detectors are the two ordered-statistic CFARs; this is the cell-averaging family
