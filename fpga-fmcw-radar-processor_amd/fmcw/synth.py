@@ -110,3 +110,186 @@ def golden_chirp_frame(samples: np.ndarray, n_chirps: int = 128, n_samples: int 
     s = np.asarray(samples)
     z = (s[:n_samples, 0] + 1j * s[:n_samples, 1]).astype(np.complex64)
     return np.broadcast_to(z, (1, n_chirps, n_samples)).copy()
+
+
+# ---- the tactical scenario (rtl/src/tb_tactical.vhd) ---------------------------------------------
+# constants of tb_tactical.vhd:28-62 (QUICK_MODE column where the testbench has two)
+TAC_WAVELENGTH = 0.1
+TAC_MAX_RANGE_M = 120000.0
+TAC_MACH_MPS = 340.29
+TAC_NM_TO_M = 1852.0
+TAC_SCAN_PERIOD = 1.0 / 2.0                  # SCAN_RATE 2 scans/s
+TAC_PRF_HZ = (8000.0, 9000.0, 10000.0)
+TAC_THERMAL_NOISE = 50.0
+TAC_SEA_CLUTTER = 200.0
+TAC_CLUTTER_RNG = 20000.0
+TAC_RANGE_RES = 150.0
+TAC_FTR_OFFSET = (0.0, -50.0, -50.0, -100.0, -100.0, -150.0)
+TAC_CLAMP = 32000.0
+# sea_scenario's own
+SEA_CLUTTER_RHO = 0.9
+SEA_LOW_FLYER_MPS = -60.0
+# the low flyer's amplitude in ADC counts (the clutter of its range bin is about 190 counts rms):
+# the fp64 oracle finds it in every scan behind the 2-pulse canceller and misses it in several
+# scans with MTI off, at 128 x 32 and at 256 x 64 (tests/test_scenario_host.py holds both)
+SEA_LOW_FLYER_AMP = 150.0
+
+
+def _vhdl_int(x):
+    """VHDL integer(real): nearest, halves away from zero."""
+    return np.sign(x) * np.floor(np.abs(x) + 0.5)
+
+
+def tac_rcs_to_amp(rcs: float, rng: float) -> float:
+    """tb_tactical.vhd:158-162."""
+    if rng < 1000.0:
+        return 30000.0
+    return float(np.sqrt(rcs) * 20000.0 / np.sqrt((rng / 10000.0) ** 4))
+
+
+class _TacTargets:
+    """The target states of tb_tactical.vhd:184-236: fighters at 45 NM in fingertip formation, Mach 1
+    inbound, RCS 12; attackers at 39 NM, Mach 0.65, RCS 20.  step(scan) applies the notch (radial
+    speed 0 from scan n_scans / 2 for three scans) and then the kinematics update of scan `scan`
+    (1-based), as the testbench does before it generates that scan's returns."""
+
+    def __init__(self, n_fighters: int, n_attackers: int, n_scans: int):
+        self.ftr = [[45.0 * TAC_NM_TO_M + TAC_FTR_OFFSET[i % 6], -1.0 * TAC_MACH_MPS, 12.0, True]
+                    for i in range(n_fighters)]
+        self.att = [[39.0 * TAC_NM_TO_M, -0.65 * TAC_MACH_MPS, 20.0, True] for _ in range(n_attackers)]
+        self.notch_scan = n_scans // 2
+
+    def step(self, scan: int):
+        if scan == self.notch_scan:
+            for t in self.ftr:
+                t[1] = 0.0
+        elif scan == self.notch_scan + 3:
+            for t in self.ftr:
+                t[1] = -1.0 * TAC_MACH_MPS
+        for t in self.ftr + self.att:
+            t[0] = t[0] + t[1] * TAC_SCAN_PERIOD
+            if t[0] < 5000.0:
+                t[3] = False
+        return [t for t in self.ftr + self.att if t[3]]     # (range_m, vel_radial, rcs, active)
+
+
+def tb_tactical_scans(n_scans: int = 5, quick: bool = True):
+    """The stimulus of rtl/src/tb_tactical.vhd:129-323, n_scans scans (NUM_SCANS; the notch is at
+    n_scans / 2).  Per scan: PRF_HZ((scan - 1) mod 3), the notch and kinematics update (:213-236),
+    then chirp outer / sample inner (:247-319): every active target whose range bin lies within 2
+    samples of the fast-time index s adds amplitude (x 0.3 / |s - bin| off the bin) at phase
+    2 pi (bin s / N_RANGE + doppler_bin c / N_DOPPLER) (:252-287; vel_to_doppler_bin adds
+    N_DOPPLER / 2, :164-171); sea clutter while s x 150 < 20000 from two UNIFORM draws (:289-298);
+    thermal noise from gauss (:149-156: two draws, u1 floored at 1e-10); clamp to +-32000
+    (:306-309) and integer() rounding (:311-312).  All draws come from one ieee_uniform stream
+    seeded (42, 42) that runs on from scan to scan.
+
+    quick=True is the QUICK_MODE shape: 128 samples x 32 chirps, 2 fighters, 1 attacker.
+    Returns (int16 [scan][1][chirp][sample][2] = (I, Q), truth): truth[scan] lists (range_bin,
+    doppler_bin) per active target, fighters first."""
+    ns, nc, n_ftr, n_att = (128, 32, 2, 1) if quick else (1024, 128, 6, 4)
+    tg = _TacTargets(n_ftr, n_att, n_scans)
+    s = np.arange(ns, dtype=np.float64)
+    c = np.arange(nc, dtype=np.float64)[:, None]
+    clut = s * TAC_RANGE_RES < TAC_CLUTTER_RNG                     # samples that take clutter draws
+    # positions of a chirp's draws: clutter samples take 4 (amplitude, phase, u1, u2), the rest 2
+    first = np.concatenate([[0], np.cumsum(np.where(clut, 4, 2))])
+    per_chirp = int(first[-1])
+    first = first[:-1]
+    i_amp, i_ph = first[clut], first[clut] + 1
+    i_u1 = first + np.where(clut, 2, 0)
+    s1 = s2 = 42
+    cubes = np.empty((n_scans, 1, nc, ns, 2), np.int16)
+    truth = []
+    for scan in range(1, n_scans + 1):
+        prf = TAC_PRF_HZ[(scan - 1) % 3]
+        acc = np.zeros((nc, ns), np.complex128)
+        bins = []
+        for rng_m, vel, rcs, _ in tg.step(scan):
+            rb = int(_vhdl_int(rng_m / TAC_MAX_RANGE_M * ns))
+            db = int(_vhdl_int(2.0 * vel / TAC_WAVELENGTH / prf * nc)) + nc // 2
+            db += nc if db < 0 else -nc if db >= nc else 0
+            bins.append((rb, db))
+            off = np.abs(s - rb)
+            amp = tac_rcs_to_amp(rcs, rng_m) * np.where(off == 0, 1.0, 0.3 / np.maximum(off, 1.0)) * (off < 3)
+            acc += amp[None, :] * np.exp(2j * np.pi * (rb * s[None, :] / ns + db * c / nc))
+        truth.append(bins)
+        u, s1, s2 = ieee_uniform(s1, s2, nc * per_chirp)
+        u = u.reshape(nc, per_chirp)
+        sc = s[clut]
+        amp = TAC_SEA_CLUTTER * (1.0 - sc / ns) * u[:, i_amp]
+        ph = 2.0 * np.pi * (sc * sc / (ns * 10) + (u[:, i_ph] - 0.5) * 4.0 * c / nc)
+        acc[:, clut] += amp * np.exp(1j * ph)
+        u1 = np.maximum(u[:, i_u1], 1.0e-10)
+        acc += TAC_THERMAL_NOISE * np.sqrt(-2.0 * np.log(u1)) * np.exp(2j * np.pi * u[:, i_u1 + 1])
+        cubes[scan - 1, 0, ..., 0] = _vhdl_int(np.clip(acc.real, -TAC_CLAMP, TAC_CLAMP))
+        cubes[scan - 1, 0, ..., 1] = _vhdl_int(np.clip(acc.imag, -TAC_CLAMP, TAC_CLAMP))
+    return cubes, truth
+
+
+def sea_clutter_edge(n_range: int) -> int:
+    """First range bin without sea clutter: the testbench's 20 km of 120 km."""
+    return int(round(n_range / 6))
+
+
+def sea_clutter(rng: np.random.Generator, n_range: int, n_doppler: int) -> np.ndarray:
+    """One scan's sea clutter [chirp][sample] complex128 (see sea_scenario): per range bin below the
+    edge an AR(1) sequence over the chirps, drawn as standard_normal((edge, n_doppler, 2))."""
+    edge = sea_clutter_edge(n_range)
+    r = np.arange(edge, dtype=np.float64)
+    w = rng.standard_normal((edge, n_doppler, 2))
+    w = (w[..., 0] + 1j * w[..., 1]) * np.sqrt(0.5)                # unit variance
+    g = np.empty((edge, n_doppler), np.complex128)
+    g[:, 0] = w[:, 0]
+    for k in range(1, n_doppler):
+        g[:, k] = SEA_CLUTTER_RHO * g[:, k - 1] + np.sqrt(1.0 - SEA_CLUTTER_RHO ** 2) * w[:, k]
+    to_fast = np.exp(2j * np.pi * r[:, None] * np.arange(n_range, dtype=np.float64)[None, :] / n_range)
+    return (TAC_SEA_CLUTTER * (1.0 - r / n_range)[:, None] * g).T @ to_fast
+
+
+def sea_scenario(n_range: int, n_doppler: int, n_scans: int, seed: int, low_flyer: bool = True):
+    """tb_tactical's scenario (2 fighters, 1 attacker, the 3-PRF stagger, the notch at n_scans / 2
+    for three scans) with its geometry meant in the range-bin domain:
+
+      targets   tones over the whole chirp at the fractional range bin range_m / 120000 n_range
+                and the fractional Doppler bin (2 v / 0.1 / prf n_doppler) mod n_doppler,
+                amplitude tac_rcs_to_amp;
+      clutter   for range bins r < edge = sea_clutter_edge(n_range): a complex Gaussian amplitude
+                per chirp, AR(1) across chirps (rho 0.9, unit variance, stationary from chirp 0),
+                times 200 (1 - r / n_range), brought to fast time by one matrix product with
+                exp(2 pi i r n / n_range); nothing at or beyond edge;
+      low flyer one more tone at range bin edge // 2 (it stays there), -60 m/s, SEA_LOW_FLYER_AMP;
+      noise     Gaussian, sigma 50 per component; then clamp to +-32000 and integer() rounding.
+
+    RNG: one numpy PCG64 generator from `seed` for the whole scene; per scan, in this order:
+    standard_normal((edge, n_doppler, 2)) for the clutter's innovations (chirp 0 first), then
+    standard_normal((n_doppler, n_range, 2)) for the noise.
+
+    Returns (int16 [scan][1][chirp][sample][2], truth) as tb_tactical_scans does; truth holds the
+    nearest bins (fighters, attacker, low flyer)."""
+    ns, nc = n_range, n_doppler
+    edge = sea_clutter_edge(ns)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    tg = _TacTargets(2, 1, n_scans)
+    n = np.arange(ns, dtype=np.float64)[None, :]
+    c = np.arange(nc, dtype=np.float64)[:, None]
+    cubes = np.empty((n_scans, 1, nc, ns, 2), np.int16)
+    truth = []
+    for scan in range(1, n_scans + 1):
+        prf = TAC_PRF_HZ[(scan - 1) % 3]
+        tones = [(rng_m / TAC_MAX_RANGE_M * ns, vel, tac_rcs_to_amp(rcs, rng_m)) for rng_m, vel, rcs, _ in tg.step(scan)]
+        if low_flyer:
+            tones.append((float(edge // 2), SEA_LOW_FLYER_MPS, SEA_LOW_FLYER_AMP))
+        acc = np.zeros((nc, ns), np.complex128)
+        bins = []
+        for rb, vel, amp in tones:
+            db = (2.0 * vel / TAC_WAVELENGTH / prf * nc) % nc
+            bins.append((int(round(rb)), int(round(db)) % nc))
+            acc += amp * np.exp(2j * np.pi * (rb * n / ns + db * c / nc))
+        truth.append(bins)
+        acc += sea_clutter(rng, ns, nc)
+        w = rng.standard_normal((nc, ns, 2))
+        acc += TAC_THERMAL_NOISE * (w[..., 0] + 1j * w[..., 1])
+        cubes[scan - 1, 0, ..., 0] = _vhdl_int(np.clip(acc.real, -TAC_CLAMP, TAC_CLAMP))
+        cubes[scan - 1, 0, ..., 1] = _vhdl_int(np.clip(acc.imag, -TAC_CLAMP, TAC_CLAMP))
+    return cubes, truth
