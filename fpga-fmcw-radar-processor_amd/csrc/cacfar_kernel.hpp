@@ -210,17 +210,8 @@ constexpr int kCaScanNT = 1024;
 __global__ void __launch_bounds__(kCaScanNT)
 k_cacfar_scan(const uint32_t* __restrict__ counts, uint32_t* __restrict__ offs, int n_tiles,
               uint32_t* __restrict__ status) {
-  __shared__ int s_wave[kCaScanNT / 64 + 1];
-  uint32_t carry = 0;
-  for (int base = 0; base < n_tiles; base += kCaScanNT) {
-    const int i = base + (int)threadIdx.x;
-    const int v = i < n_tiles ? (int)counts[i] : 0;   // a tile has at most 2^16 cells
-    int total;
-    const int ex = block_excl_scan<kCaScanNT>(v, s_wave, total);
-    if (i < n_tiles) offs[i] = carry + (uint32_t)ex;
-    carry += (uint32_t)total;
-  }
-  if (threadIdx.x < FMCW_STATUS_WORDS) status[threadIdx.x] = threadIdx.x == 0 ? carry : 0u;
+  const uint32_t sum = tile_offsets_scan<kCaScanNT>(counts, offs, n_tiles);   // a tile has at most 2^16 cells
+  if (threadIdx.x < FMCW_STATUS_WORDS) status[threadIdx.x] = threadIdx.x == 0 ? sum : 0u;
 }
 
 }  // namespace fmcw

@@ -275,17 +275,8 @@ constexpr int kCmScanNT = 1024;
 __global__ void __launch_bounds__(kCmScanNT)
 k_cmap_scan(const uint32_t* __restrict__ counts, uint32_t* __restrict__ offs, int n_tiles, uint32_t* __restrict__ status,
             uint32_t* __restrict__ ctl, int n_streams, uint32_t n_scans) {
-  __shared__ int s_wave[kCmScanNT / 64 + 1];
-  uint32_t carry = 0;
-  for (int base = 0; base < n_tiles; base += kCmScanNT) {
-    const int i = base + (int)threadIdx.x;
-    const int v = i < n_tiles ? (int)counts[i] : 0;   // a tile has at most 8192 cells
-    int total;
-    const int ex = block_excl_scan<kCmScanNT>(v, s_wave, total);
-    if (i < n_tiles) offs[i] = carry + (uint32_t)ex;
-    carry += (uint32_t)total;
-  }
-  if (threadIdx.x < FMCW_STATUS_WORDS) status[threadIdx.x] = threadIdx.x == 0 ? carry : 0u;
+  const uint32_t sum = tile_offsets_scan<kCmScanNT>(counts, offs, n_tiles);   // a tile has at most 8192 cells
+  if (threadIdx.x < FMCW_STATUS_WORDS) status[threadIdx.x] = threadIdx.x == 0 ? sum : 0u;
   if (n_scans) {
     for (int b = (int)threadIdx.x; b < n_streams; b += kCmScanNT) {
       const uint32_t a = ctl[2 + b];

@@ -81,6 +81,26 @@ __device__ __forceinline__ int block_excl_scan(int v, int* s_wave, int& total) {
   return r;
 }
 
+// The scan between a detector's count pass and its emit pass, for one workgroup of NT threads:
+// offs[i] = counts[0] + .. + counts[i-1] for i < n_tiles; returns the sum of all counts, in every
+// thread.  Rounds of NT tiles, the running total carried from one round to the next.  counts may be
+// offs (a thread reads its element before it writes it, and no other thread touches that element),
+// hence no __restrict__.  A round's counts sum to less than 2^31.
+template <int NT>
+__device__ __forceinline__ uint32_t tile_offsets_scan(const uint32_t* counts, uint32_t* offs, int n_tiles) {
+  __shared__ int s_wave[NT / 64 + 1];
+  uint32_t carry = 0;
+  for (int base = 0; base < n_tiles; base += NT) {
+    const int i = base + (int)threadIdx.x;
+    const int v = i < n_tiles ? (int)counts[i] : 0;
+    int total;
+    const int ex = block_excl_scan<NT>(v, s_wave, total);
+    if (i < n_tiles) offs[i] = carry + (uint32_t)ex;
+    carry += (uint32_t)total;
+  }
+  return carry;
+}
+
 // Wave-level exclusive scan; `total` = the wave's sum, uniform.  DPP adds on the VALU (GCN
 // row scan: row_shr 1/2/4/8 inside each row of 16 lanes, then row_bcast:15 / row_bcast:31 carry
 // the row totals), where the former __shfl_up version took six ds_bpermute round trips through

@@ -12,7 +12,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 
 #include "adapt_kernel.hpp"
 #include "internal.hpp"
@@ -33,13 +32,8 @@ AccFn pick_mti(int mti) {
                                   : fmcw::k_adapt_acc<ROWS, FMCW_MTI_3PULSE>;
 }
 
-bool pow2(uint32_t x) { return x && !(x & (x - 1)); }
-
 int validate(const fmcw_adapt_config& c) {
-  if (!pow2(c.n_range) || c.n_range < 64 || c.n_range > 8192)
-    return fail(FMCW_EINVAL, "n_range=%u: must be a power of two in [64, 8192]", c.n_range);
-  if (!pow2(c.n_doppler) || c.n_doppler < 32 || c.n_doppler > 1024)
-    return fail(FMCW_EINVAL, "n_doppler=%u: must be a power of two in [32, 1024]", c.n_doppler);
+  if (int rc = fmcw::check_map_dims(c.n_range, c.n_doppler)) return rc;
   if (c.n_rx < 1 || c.n_rx > 16) return fail(FMCW_EINVAL, "n_rx=%u: must be in [1, 16] (17..64 is not built)", c.n_rx);
   if (c.n_beams < 1 || c.n_beams > 64) return fail(FMCW_EINVAL, "n_beams=%u: must be in [1, 64]", c.n_beams);
   if (c.mti_mode != FMCW_MTI_OFF && c.mti_mode != FMCW_MTI_2PULSE && c.mti_mode != FMCW_MTI_3PULSE)
@@ -52,7 +46,7 @@ int validate(const fmcw_adapt_config& c) {
   if (!std::isfinite(c.loading) || c.loading < 0.f)
     return fail(FMCW_EINVAL, "loading %g: must be finite and >= 0", (double)c.loading);
   if (c.reserved != 0) return fail(FMCW_EINVAL, "reserved %u: must be 0", c.reserved);
-  if (c.device_id < 0 || c.device_id > 63) return fail(FMCW_EINVAL, "device_id %d (0..63)", c.device_id);
+  if (int rc = fmcw::check_device_id(c.device_id)) return rc;
   return FMCW_OK;
 }
 
@@ -88,7 +82,7 @@ void fmcw_adapt_config_default(fmcw_adapt_config* cfg) {
 int fmcw_adapt_create(const fmcw_adapt_config* cfg, const float* a_host, fmcw_adapt** out) {
   if (!cfg || !out) return fail(FMCW_EINVAL, "null argument");
   *out = nullptr;
-  const int rc = validate(*cfg);
+  int rc = validate(*cfg);
   if (rc) return rc;
   if (!a_host) return fail(FMCW_EINVAL, "null a_host");
   for (uint32_t b = 0; b < cfg->n_beams; ++b) {
@@ -101,19 +95,7 @@ int fmcw_adapt_create(const fmcw_adapt_config* cfg, const float* a_host, fmcw_ad
       }
     if (!any) return fail(FMCW_EINVAL, "a_host: beam %u is all zero (no look direction to hold at unit gain)", b);
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    (void)hipGetLastError();
-    return fail(FMCW_ENODEV, "no HIP device");
-  }
-  if (cfg->device_id >= ndev) return fail(FMCW_ENODEV, "device_id %d out of range", cfg->device_id);
-  hipDeviceProp_t prop;
-  if (hipSetDevice(cfg->device_id) != hipSuccess || hipGetDeviceProperties(&prop, cfg->device_id) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(FMCW_ENODEV, "device_id %d", cfg->device_id);
-  }
-  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(FMCW_ENODEV, "device %d is %s; this build targets gfx950 (MI355X)", cfg->device_id, prop.gcnArchName);
+  if ((rc = fmcw::open_device(cfg->device_id))) return rc;
   fmcw_adapt* a = new fmcw_adapt();
   a->cfg = *cfg;
   a->rows = cfg->n_rx <= 8 ? 16 : 32;
@@ -151,7 +133,7 @@ int fmcw_adapt_destroy(fmcw_adapt* a) {
 
 int fmcw_adapt_set_grid_for_test(fmcw_adapt* a, uint32_t grid) {
   if (!a) return fail(FMCW_EINVAL, "null adaptive-weights object");
-  a->grid = grid ? std::min(a->max_grid, grid) : a->max_grid;
+  a->grid = fmcw::clamp_grid(grid, a->max_grid);
   return FMCW_OK;
 }
 
@@ -161,10 +143,10 @@ int fmcw_adapt_enqueue(fmcw_adapt* a, const void* spec_dev, size_t n_frames, voi
   if (n_frames == 0) return FMCW_OK;
   if (!spec_dev || !w_dev || !info_dev)
     return fail(FMCW_EINVAL, "null spec_dev, w_dev or info_dev with n_frames %zu", n_frames);
-  if (reinterpret_cast<uintptr_t>(spec_dev) & 7u) return fail(FMCW_EINVAL, "spec_dev must be 8-byte aligned");
-  if (reinterpret_cast<uintptr_t>(w_dev) & 7u) return fail(FMCW_EINVAL, "w_dev must be 8-byte aligned");
-  if (reinterpret_cast<uintptr_t>(cov_dev) & 15u) return fail(FMCW_EINVAL, "cov_dev must be 16-byte aligned");
-  if (reinterpret_cast<uintptr_t>(info_dev) & 3u) return fail(FMCW_EINVAL, "info_dev must be 4-byte aligned");
+  if (int rc = fmcw::aligned(spec_dev, 8, "spec_dev")) return rc;
+  if (int rc = fmcw::aligned(w_dev, 8, "w_dev")) return rc;
+  if (int rc = fmcw::aligned(cov_dev, 16, "cov_dev")) return rc;
+  if (int rc = fmcw::aligned(info_dev, 4, "info_dev")) return rc;
   const fmcw_adapt_config& c = a->cfg;
   fmcw::AdaptGeom g;
   g.nd = c.n_doppler;
@@ -183,11 +165,11 @@ int fmcw_adapt_enqueue(fmcw_adapt* a, const void* spec_dev, size_t n_frames, voi
   const uint32_t n_wg = std::min((g.n_units + fmcw::kAdaptWaves - 1) / fmcw::kAdaptWaves, a->grid);
   hipLaunchKernelGGL(a->acc, dim3(n_wg), dim3(fmcw::kAdaptThreads), 0, s, static_cast<const float2*>(spec_dev), g,
                      a->part);
-  if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_adapt_acc launch");
+  if (int rc = fmcw::check_launch("k_adapt_acc")) return rc;
   const uint32_t n_parts = std::min(g.n_units, (uint32_t)fmcw::kAdaptFoldParts);
   hipLaunchKernelGGL(fmcw::k_adapt_fold, dim3(n_parts), dim3(256), 0, s, static_cast<const float*>(a->part), g.n_units,
                      n_parts, a->rows * a->rows, a->part2);
-  if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_adapt_fold launch");
+  if (int rc = fmcw::check_launch("k_adapt_fold")) return rc;
   fmcw::SolveArgs p;
   p.nrx = c.n_rx;
   p.nb = c.n_beams;
@@ -199,8 +181,7 @@ int fmcw_adapt_enqueue(fmcw_adapt* a, const void* spec_dev, size_t n_frames, voi
   hipLaunchKernelGGL(fmcw::k_adapt_solve, dim3(1), dim3(fmcw::kSolveThreads), 0, s,
                      static_cast<const double*>(a->part2), static_cast<const float2*>(a->a), p,
                      static_cast<float2*>(w_dev), static_cast<double2*>(cov_dev), info_dev);
-  if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_adapt_solve launch");
-  return FMCW_OK;
+  return fmcw::check_launch("k_adapt_solve");
 }
 
 }  // extern "C"

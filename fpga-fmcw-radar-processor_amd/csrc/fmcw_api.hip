@@ -168,6 +168,8 @@ int fmcw_create(const fmcw_config* cfg, fmcw_handle** out) {
   *out = nullptr;
   int rc = validate(*cfg);
   if (rc) return rc;
+  // not open_device(): validate() leaves device_id to this sequence (a negative one is FMCW_ENODEV
+  // here), and a device that cannot be selected or queried is FMCW_EHIP with the HIP error's text
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
     (void)hipGetLastError();

@@ -10,7 +10,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 #include <vector>
 
 #include "beam_kernel.hpp"
@@ -49,13 +48,8 @@ BeamKernel pick(uint32_t nd, int mti) {
   }
 }
 
-bool pow2(uint32_t x) { return x && !(x & (x - 1)); }
-
 int validate(const fmcw_beams_config& c) {
-  if (!pow2(c.n_range) || c.n_range < 64 || c.n_range > 8192)
-    return fail(FMCW_EINVAL, "n_range=%u: must be a power of two in [64, 8192]", c.n_range);
-  if (!pow2(c.n_doppler) || c.n_doppler < 32 || c.n_doppler > 1024)
-    return fail(FMCW_EINVAL, "n_doppler=%u: must be a power of two in [32, 1024]", c.n_doppler);
+  if (int rc = fmcw::check_map_dims(c.n_range, c.n_doppler)) return rc;
   if (c.n_rx < 1 || c.n_rx > 64) return fail(FMCW_EINVAL, "n_rx=%u: must be in [1, 64]", c.n_rx);
   if (c.n_beams < 1 || c.n_beams > 64) return fail(FMCW_EINVAL, "n_beams=%u: must be in [1, 64]", c.n_beams);
   if (c.window != FMCW_WIN_NONE && c.window != FMCW_WIN_HAMMING)
@@ -63,7 +57,7 @@ int validate(const fmcw_beams_config& c) {
   if (c.mti_mode != FMCW_MTI_OFF && c.mti_mode != FMCW_MTI_2PULSE && c.mti_mode != FMCW_MTI_3PULSE)
     return fail(FMCW_EINVAL, "mti_mode %d (0, 2, 3)", c.mti_mode);
   if (c.reserved != 0) return fail(FMCW_EINVAL, "reserved %u: must be 0", c.reserved);
-  if (c.device_id < 0 || c.device_id > 63) return fail(FMCW_EINVAL, "device_id %d (0..63)", c.device_id);
+  if (int rc = fmcw::check_device_id(c.device_id)) return rc;
   return FMCW_OK;
 }
 
@@ -95,38 +89,21 @@ void fmcw_beams_config_default(fmcw_beams_config* cfg) {
 int fmcw_beams_create(const fmcw_beams_config* cfg, const float* weights_host, fmcw_beams** out) {
   if (!cfg || !out) return fail(FMCW_EINVAL, "null argument");
   *out = nullptr;
-  const int rc = validate(*cfg);
+  int rc = validate(*cfg);
   if (rc) return rc;
   if (!weights_host) return fail(FMCW_EINVAL, "null weights_host");
   const size_t nw = (size_t)cfg->n_beams * cfg->n_rx;
   for (size_t i = 0; i < 2 * nw; ++i)
     if (!std::isfinite(weights_host[i]))
       return fail(FMCW_EINVAL, "weights_host: beam %zu, rx %zu is not finite", i / 2 / cfg->n_rx, i / 2 % cfg->n_rx);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    (void)hipGetLastError();
-    return fail(FMCW_ENODEV, "no HIP device");
-  }
-  if (cfg->device_id >= ndev) return fail(FMCW_ENODEV, "device_id %d out of range", cfg->device_id);
   hipDeviceProp_t prop;
-  if (hipSetDevice(cfg->device_id) != hipSuccess || hipGetDeviceProperties(&prop, cfg->device_id) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(FMCW_ENODEV, "device_id %d", cfg->device_id);
-  }
-  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(FMCW_ENODEV, "device %d is %s; this build targets gfx950 (MI355X)", cfg->device_id, prop.gcnArchName);
+  if ((rc = fmcw::open_device(cfg->device_id, &prop))) return rc;
   const uint32_t nd = cfg->n_doppler;
   const std::vector<float> win = fmcw::window_table(nd, cfg->window);
   fmcw_beams* b = new fmcw_beams();
   b->cfg = *cfg;
   b->k = pick(nd, cfg->mti_mode);
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(b->k.fn), b->k.NT, 0) !=
-          hipSuccess || per_cu < 1) {
-    (void)hipGetLastError();
-    per_cu = 1;
-  }
-  b->max_grid = b->grid = (uint32_t)per_cu * (uint32_t)std::max(prop.multiProcessorCount, 1);
+  b->max_grid = b->grid = fmcw::resident_grid(reinterpret_cast<const void*>(b->k.fn), b->k.NT, 0, prop);
   if (hipMalloc(reinterpret_cast<void**>(&b->w), nw * sizeof(float2)) != hipSuccess ||
       hipMalloc(reinterpret_cast<void**>(&b->win), nd * sizeof(float)) != hipSuccess) {
     (void)hipGetLastError();
@@ -154,14 +131,14 @@ int fmcw_beams_destroy(fmcw_beams* b) {
 
 int fmcw_beams_set_grid_for_test(fmcw_beams* b, uint32_t grid) {
   if (!b) return fail(FMCW_EINVAL, "null beamformer");
-  b->grid = grid ? std::min(b->max_grid, grid) : b->max_grid;
+  b->grid = fmcw::clamp_grid(grid, b->max_grid);
   return FMCW_OK;
 }
 
 int fmcw_beams_set_weights_dev(fmcw_beams* b, const void* w_dev, void* stream) {
   if (!b) return fail(FMCW_EINVAL, "null beamformer");
   if (!w_dev) return fail(FMCW_EINVAL, "null w_dev");
-  if (reinterpret_cast<uintptr_t>(w_dev) & 7u) return fail(FMCW_EINVAL, "w_dev must be 8-byte aligned");
+  if (int rc = fmcw::aligned(w_dev, 8, "w_dev")) return rc;
   if (hipSetDevice(b->cfg.device_id) != hipSuccess) return fail(FMCW_EHIP, "hipSetDevice");
   HIP_TRY(hipMemcpyAsync(b->w, w_dev, (size_t)b->cfg.n_beams * b->cfg.n_rx * sizeof(float2), hipMemcpyDeviceToDevice,
                          reinterpret_cast<hipStream_t>(stream)));
@@ -172,8 +149,8 @@ int fmcw_beams_enqueue(fmcw_beams* b, const void* spec_dev, size_t n_frames, flo
   if (!b) return fail(FMCW_EINVAL, "null beamformer");
   if (n_frames == 0) return FMCW_OK;
   if (!spec_dev || !maps_dev) return fail(FMCW_EINVAL, "null spec_dev or maps_dev with n_frames %zu", n_frames);
-  if (reinterpret_cast<uintptr_t>(maps_dev) & 15u) return fail(FMCW_EINVAL, "maps_dev must be 16-byte aligned");
-  if (reinterpret_cast<uintptr_t>(spec_dev) & 7u) return fail(FMCW_EINVAL, "spec_dev must be 8-byte aligned");
+  if (int rc = fmcw::aligned(maps_dev, 16, "maps_dev")) return rc;
+  if (int rc = fmcw::aligned(spec_dev, 8, "spec_dev")) return rc;
   const fmcw_beams_config& c = b->cfg;
   const size_t tiles_frame = c.n_range / (uint32_t)b->k.WR;
   if (n_frames > 0x7fffffffu / tiles_frame)
@@ -185,8 +162,7 @@ int fmcw_beams_enqueue(fmcw_beams* b, const void* spec_dev, size_t n_frames, flo
   hipLaunchKernelGGL(b->k.fn, dim3(n_wg), dim3(b->k.NT), 0, reinterpret_cast<hipStream_t>(stream),
                      static_cast<const float2*>(spec_dev), static_cast<const float2*>(b->w),
                      static_cast<const float*>(b->win), (int)c.n_range, (int)c.n_rx, (int)c.n_beams, n_tiles, maps_dev);
-  if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_beams launch");
-  return FMCW_OK;
+  return fmcw::check_launch("k_beams");
 }
 
 }  // extern "C"

@@ -27,7 +27,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 #include <vector>
 
 #include "internal.hpp"
@@ -177,13 +176,8 @@ __global__ void __launch_bounds__(64) k_bearings_status(uint32_t cap, const uint
   }
 }
 
-bool pow2(uint32_t x) { return x && !(x & (x - 1)); }
-
 int validate(const fmcw_bearings_config& c) {
-  if (!pow2(c.n_range) || c.n_range < 64 || c.n_range > 8192)
-    return fail(FMCW_EINVAL, "n_range=%u: must be a power of two in [64, 8192]", c.n_range);
-  if (!pow2(c.n_doppler) || c.n_doppler < 32 || c.n_doppler > 1024)
-    return fail(FMCW_EINVAL, "n_doppler=%u: must be a power of two in [32, 1024]", c.n_doppler);
+  if (int rc = fmcw::check_map_dims(c.n_range, c.n_doppler)) return rc;
   if (c.n_rx < 1 || c.n_rx > 64) return fail(FMCW_EINVAL, "n_rx=%u: must be in [1, 64]", c.n_rx);
   if (c.window != FMCW_WIN_NONE && c.window != FMCW_WIN_HAMMING)
     return fail(FMCW_EINVAL, "window %d: the bearing estimator has the float windows only (NONE, HAMMING)", c.window);
@@ -193,7 +187,7 @@ int validate(const fmcw_bearings_config& c) {
     return fail(FMCW_EINVAL, "spacing %g: must be positive and finite (wavelengths)", (double)c.spacing);
   if (c.max_records < 1 || c.max_records > 0x7fffffffu)
     return fail(FMCW_EINVAL, "max_records %u (1..2^31-1)", c.max_records);
-  if (c.device_id < 0 || c.device_id > 63) return fail(FMCW_EINVAL, "device_id %d (0..63)", c.device_id);
+  if (int rc = fmcw::check_device_id(c.device_id)) return rc;
   return FMCW_OK;
 }
 
@@ -224,21 +218,9 @@ void fmcw_bearings_config_default(fmcw_bearings_config* cfg) {
 int fmcw_bearings_create(const fmcw_bearings_config* cfg, fmcw_bearings** out) {
   if (!cfg || !out) return fail(FMCW_EINVAL, "null argument");
   *out = nullptr;
-  const int rc = validate(*cfg);
+  int rc = validate(*cfg);
   if (rc) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    (void)hipGetLastError();
-    return fail(FMCW_ENODEV, "no HIP device");
-  }
-  if (cfg->device_id >= ndev) return fail(FMCW_ENODEV, "device_id %d out of range", cfg->device_id);
-  hipDeviceProp_t prop;
-  if (hipSetDevice(cfg->device_id) != hipSuccess || hipGetDeviceProperties(&prop, cfg->device_id) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(FMCW_ENODEV, "device_id %d", cfg->device_id);
-  }
-  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(FMCW_ENODEV, "device %d is %s; this build targets gfx950 (MI355X)", cfg->device_id, prop.gcnArchName);
+  if ((rc = fmcw::open_device(cfg->device_id))) return rc;
   const uint32_t nd = cfg->n_doppler;
   std::vector<float2> tw(nd);
   for (uint32_t m = 0; m < nd; ++m) {
@@ -277,7 +259,7 @@ int fmcw_bearings_destroy(fmcw_bearings* b) {
 
 int fmcw_bearings_set_grid_for_test(fmcw_bearings* b, uint32_t grid) {
   if (!b) return fail(FMCW_EINVAL, "null bearing estimator");
-  b->grid = grid ? std::min(kMaxGrid, grid) : kMaxGrid;
+  b->grid = fmcw::clamp_grid(grid, kMaxGrid);
   return FMCW_OK;
 }
 
@@ -304,11 +286,10 @@ int fmcw_bearings_enqueue(fmcw_bearings* b, const void* spec_dev, size_t n_frame
     hipLaunchKernelGGL(kern, dim3(n_wg), dim3(kThreads), 0, s, static_cast<const float2*>(spec_dev),
                        static_cast<const uint8_t*>(records_dev), (uint32_t)rec_stride, cap, n_records_dev, g, b->tw,
                        b->win, bearings_dev, static_cast<float2*>(snaps_dev), b->wg_bad);
-    if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_bearings launch");
+    if (int rc = fmcw::check_launch("k_bearings")) return rc;
   }
   hipLaunchKernelGGL(k_bearings_status, dim3(1), dim3(64), 0, s, cap, n_records_dev, b->wg_bad, n_wg, n_out_dev);
-  if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_bearings_status launch");
-  return FMCW_OK;
+  return fmcw::check_launch("k_bearings_status");
 }
 
 }  // extern "C"

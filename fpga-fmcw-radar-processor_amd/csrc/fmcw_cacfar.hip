@@ -9,7 +9,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 
 #include "cacfar_kernel.hpp"
 #include "internal.hpp"
@@ -20,9 +19,8 @@ static_assert(sizeof(fmcw_cacfar_config) == 48, "fmcw.h cell-averaging detector 
 
 namespace {
 
-bool pow2(uint32_t x) { return x && !(x & (x - 1)); }
-
-constexpr size_t kMaxLdsBytes = (size_t)(25 + 9 + 2) * 1024 * sizeof(float);   // 144 KiB of the CU's 160
+// the largest any configuration needs (n_doppler 1024, window 8/4): 144 KiB of the CU's 160
+constexpr size_t kMaxLdsBytes = (size_t)(25 + 9 + 2) * 1024 * sizeof(float);
 
 // N of the window, in 64 bits (the fields are unchecked when it is first needed)
 uint64_t n_ref(const fmcw_cacfar_config& c) {
@@ -31,10 +29,7 @@ uint64_t n_ref(const fmcw_cacfar_config& c) {
 }
 
 int validate(const fmcw_cacfar_config& c) {
-  if (!pow2(c.n_range) || c.n_range < 64 || c.n_range > 8192)
-    return fail(FMCW_EINVAL, "n_range=%u: must be a power of two in [64, 8192]", c.n_range);
-  if (!pow2(c.n_doppler) || c.n_doppler < 32 || c.n_doppler > 1024)
-    return fail(FMCW_EINVAL, "n_doppler=%u: must be a power of two in [32, 1024]", c.n_doppler);
+  if (int rc = fmcw::check_map_dims(c.n_range, c.n_doppler)) return rc;
   if (c.mode != FMCW_CACFAR_CA && c.mode != FMCW_CACFAR_GO && c.mode != FMCW_CACFAR_SO)
     return fail(FMCW_EINVAL, "mode %d (0 CA, 1 GO, 2 SO)", c.mode);
   if (c.ref_range > 8) return fail(FMCW_EINVAL, "ref_range %u (0..8)", c.ref_range);
@@ -53,7 +48,7 @@ int validate(const fmcw_cacfar_config& c) {
   if (!std::isfinite(c.alpha) || !(c.alpha > 0.f)) return fail(FMCW_EINVAL, "alpha %g: must be finite and > 0", c.alpha);
   if (c.max_frames < 1 || (uint64_t)c.max_frames * c.n_range * c.n_doppler >= (1ull << 32))
     return fail(FMCW_EINVAL, "max_frames %u: need 1 <= max_frames and max_frames x cells < 2^32", c.max_frames);
-  if (c.device_id < 0 || c.device_id > 63) return fail(FMCW_EINVAL, "device_id %d (0..63)", c.device_id);
+  if (int rc = fmcw::check_device_id(c.device_id)) return rc;
   if (c.reserved[0] != 0 || c.reserved[1] != 0)
     return fail(FMCW_EINVAL, "reserved {%u, %u}: must be 0", c.reserved[0], c.reserved[1]);
   return FMCW_OK;
@@ -94,21 +89,10 @@ void fmcw_cacfar_config_default(fmcw_cacfar_config* cfg) {
 int fmcw_cacfar_create(const fmcw_cacfar_config* cfg, fmcw_cacfar** out) {
   if (!cfg || !out) return fail(FMCW_EINVAL, "null argument");
   *out = nullptr;
-  const int rc = validate(*cfg);
+  int rc = validate(*cfg);
   if (rc) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    (void)hipGetLastError();
-    return fail(FMCW_ENODEV, "no HIP device");
-  }
-  if (cfg->device_id >= ndev) return fail(FMCW_ENODEV, "device_id %d out of range", cfg->device_id);
   hipDeviceProp_t prop;
-  if (hipSetDevice(cfg->device_id) != hipSuccess || hipGetDeviceProperties(&prop, cfg->device_id) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(FMCW_ENODEV, "device_id %d", cfg->device_id);
-  }
-  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(FMCW_ENODEV, "device %d is %s; this build targets gfx950 (MI355X)", cfg->device_id, prop.gcnArchName);
+  if ((rc = fmcw::open_device(cfg->device_id, &prop))) return rc;
 
   fmcw_cacfar* c = new fmcw_cacfar();
   c->cfg = *cfg;
@@ -131,22 +115,13 @@ int fmcw_cacfar_create(const fmcw_cacfar_config* cfg, fmcw_cacfar** out) {
   const bool def = a.rr == 4 && a.gr == 1 && a.rd == 4 && a.gd == 2;
   c->count = def ? fmcw::k_cacfar<false, true> : fmcw::k_cacfar<false, false>;
   c->emit = def ? fmcw::k_cacfar<true, true> : fmcw::k_cacfar<true, false>;
-  int per_cu = 1;
-  for (const void* fn : {reinterpret_cast<const void*>(c->count), reinterpret_cast<const void*>(c->emit)}) {
-    // the largest any configuration needs (n_doppler 1024, window 8/4): the attribute is per kernel,
-    // not per detector, so it must not shrink when a second detector is created
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsBytes) != hipSuccess) {
-      (void)hipGetLastError();
-      delete c;
-      return fail(FMCW_EHIP, "k_cacfar: %zu B of LDS per workgroup refused", kMaxLdsBytes);
-    }
+  const void* const count = reinterpret_cast<const void*>(c->count);
+  const void* const emit = reinterpret_cast<const void*>(c->emit);
+  if ((rc = fmcw::raise_lds_limit({count, emit}, kMaxLdsBytes, "k_cacfar"))) {
+    delete c;
+    return rc;
   }
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(c->emit),
-                                                   fmcw::kCaNT, c->lds_bytes) != hipSuccess || per_cu < 1) {
-    (void)hipGetLastError();
-    per_cu = 1;
-  }
-  c->max_grid = c->grid = (uint32_t)per_cu * (uint32_t)std::max(prop.multiProcessorCount, 1);
+  c->max_grid = c->grid = fmcw::resident_grid(emit, fmcw::kCaNT, c->lds_bytes, prop);
   if (hipMalloc(reinterpret_cast<void**>(&c->tile_words), 2 * c->max_tiles * sizeof(uint32_t)) != hipSuccess) {
     (void)hipGetLastError();
     const size_t tiles = c->max_tiles;
@@ -167,7 +142,7 @@ int fmcw_cacfar_destroy(fmcw_cacfar* c) {
 
 int fmcw_cacfar_set_grid_for_test(fmcw_cacfar* c, uint32_t grid) {
   if (!c) return fail(FMCW_EINVAL, "null detector");
-  c->grid = grid ? std::min(c->max_grid, grid) : c->max_grid;
+  c->grid = fmcw::clamp_grid(grid, c->max_grid);
   return FMCW_OK;
 }
 
@@ -177,10 +152,7 @@ int fmcw_cacfar_enqueue(fmcw_cacfar* c, const float* map_dev, size_t n_frames, f
   if (!n_dets_dev) return fail(FMCW_EINVAL, "null n_dets_dev");
   if (n_frames > c->cfg.max_frames)
     return fail(FMCW_EINVAL, "n_frames %zu exceeds max_frames %u", n_frames, c->cfg.max_frames);
-  if (n_frames && !map_dev) return fail(FMCW_EINVAL, "null map_dev with n_frames %zu", n_frames);
-  if (reinterpret_cast<uintptr_t>(map_dev) & 15u) return fail(FMCW_EINVAL, "map_dev must be 16-byte aligned");
-  if (!dets_dev && det_cap) return fail(FMCW_EINVAL, "null dets_dev with det_cap %zu", det_cap);
-  if (reinterpret_cast<uintptr_t>(dets_dev) & 15u) return fail(FMCW_EINVAL, "dets_dev must be 16-byte aligned");
+  if (int rc = fmcw::check_map_and_dets(map_dev, n_frames, dets_dev, det_cap)) return rc;
   if (hipSetDevice(c->cfg.device_id) != hipSuccess) return fail(FMCW_EHIP, "hipSetDevice");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int n_tiles = (int)(n_frames * (size_t)c->args.tiles_per_frame);
@@ -192,15 +164,15 @@ int fmcw_cacfar_enqueue(fmcw_cacfar* c, const float* map_dev, size_t n_frames, f
   if (n_tiles) {
     hipLaunchKernelGGL(c->count, dim3(n_wg), dim3(fmcw::kCaNT), c->lds_bytes, s, map_dev, c->args, n_tiles,
                        counts, static_cast<const uint32_t*>(nullptr), static_cast<fmcw_det*>(nullptr), 0u);
-    if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_cacfar count launch");
+    if (int rc = fmcw::check_launch("k_cacfar count")) return rc;
   }
   hipLaunchKernelGGL(fmcw::k_cacfar_scan, dim3(1), dim3(fmcw::kCaScanNT), 0, s, static_cast<const uint32_t*>(counts),
                      offs, n_tiles, n_dets_dev);
-  if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_cacfar_scan launch");
+  if (int rc = fmcw::check_launch("k_cacfar_scan")) return rc;
   if (n_tiles && cap) {
     hipLaunchKernelGGL(c->emit, dim3(n_wg), dim3(fmcw::kCaNT), c->lds_bytes, s, map_dev, c->args, n_tiles,
                        static_cast<uint32_t*>(nullptr), static_cast<const uint32_t*>(offs), dets_dev, cap);
-    if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_cacfar emit launch");
+    if (int rc = fmcw::check_launch("k_cacfar emit")) return rc;
   }
   return FMCW_OK;
 }

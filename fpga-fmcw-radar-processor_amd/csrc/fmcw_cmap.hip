@@ -20,16 +20,11 @@ static_assert(sizeof(fmcw_cmap_config) == 64, "fmcw.h clutter map layout");
 
 namespace {
 
-bool pow2(uint32_t x) { return x && !(x & (x - 1)); }
-
 // the largest any configuration needs: n_doppler 1024 (8 owned rows), spread_range 4
 constexpr size_t kMaxLdsBytes = (size_t)(8 + 2 * fmcw::kCmMaxSpread) * 1024 * sizeof(float);
 
 int validate(const fmcw_cmap_config& c) {
-  if (!pow2(c.n_range) || c.n_range < 64 || c.n_range > 8192)
-    return fail(FMCW_EINVAL, "n_range=%u: must be a power of two in [64, 8192]", c.n_range);
-  if (!pow2(c.n_doppler) || c.n_doppler < 32 || c.n_doppler > 1024)
-    return fail(FMCW_EINVAL, "n_doppler=%u: must be a power of two in [32, 1024]", c.n_doppler);
+  if (int rc = fmcw::check_map_dims(c.n_range, c.n_doppler)) return rc;
   if (c.n_streams < 1 || c.n_streams > 64) return fail(FMCW_EINVAL, "n_streams %u (1..64)", c.n_streams);
   if (!std::isfinite(c.gain) || !(c.gain > 0.f) || c.gain > 1.f)
     return fail(FMCW_EINVAL, "gain %g: must be finite, 0 < gain <= 1", c.gain);
@@ -45,7 +40,7 @@ int validate(const fmcw_cmap_config& c) {
       (uint64_t)c.max_frames * c.n_range * c.n_doppler >= (1ull << 32))
     return fail(FMCW_EINVAL, "max_frames %u: need a multiple of n_streams %u, >= n_streams, and max_frames x cells < 2^32",
                 c.max_frames, c.n_streams);
-  if (c.device_id < 0 || c.device_id > 63) return fail(FMCW_EINVAL, "device_id %d (0..63)", c.device_id);
+  if (int rc = fmcw::check_device_id(c.device_id)) return rc;
   for (int i = 0; i < 4; ++i)
     if (c.reserved[i] != 0) return fail(FMCW_EINVAL, "reserved[%d] = %u: must be 0", i, c.reserved[i]);
   return FMCW_OK;
@@ -113,21 +108,10 @@ int fmcw_cmap_destroy(fmcw_cmap* c) {
 int fmcw_cmap_create(const fmcw_cmap_config* cfg, fmcw_cmap** out) {
   if (!cfg || !out) return fail(FMCW_EINVAL, "null argument");
   *out = nullptr;
-  const int rc = validate(*cfg);
+  int rc = validate(*cfg);
   if (rc) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    (void)hipGetLastError();
-    return fail(FMCW_ENODEV, "no HIP device");
-  }
-  if (cfg->device_id >= ndev) return fail(FMCW_ENODEV, "device_id %d out of range", cfg->device_id);
   hipDeviceProp_t prop;
-  if (hipSetDevice(cfg->device_id) != hipSuccess || hipGetDeviceProperties(&prop, cfg->device_id) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(FMCW_ENODEV, "device_id %d", cfg->device_id);
-  }
-  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(FMCW_ENODEV, "device %d is %s; this build targets gfx950 (MI355X)", cfg->device_id, prop.gcnArchName);
+  if ((rc = fmcw::open_device(cfg->device_id, &prop))) return rc;
 
   fmcw_cmap* c = new fmcw_cmap();
   c->cfg = *cfg;
@@ -149,21 +133,13 @@ int fmcw_cmap_create(const fmcw_cmap_config* cfg, fmcw_cmap** out) {
   c->lds_bytes = fmcw::cmap_lds_floats(nd, a.rows, a.sr) * sizeof(float);
   c->count = pick<false>(cfg->spread_doppler);
   c->emit = pick<true>(cfg->spread_doppler);
-  for (const void* fn : {reinterpret_cast<const void*>(c->count), reinterpret_cast<const void*>(c->emit)}) {
-    // per kernel, not per object: it must not shrink when a second map is created
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsBytes) != hipSuccess) {
-      (void)hipGetLastError();
-      delete c;
-      return fail(FMCW_EHIP, "k_cmap: %zu B of LDS per workgroup refused", kMaxLdsBytes);
-    }
+  const void* const count = reinterpret_cast<const void*>(c->count);
+  const void* const emit = reinterpret_cast<const void*>(c->emit);
+  if ((rc = fmcw::raise_lds_limit({count, emit}, kMaxLdsBytes, "k_cmap"))) {
+    delete c;
+    return rc;
   }
-  int per_cu = 1;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(c->emit), fmcw::kCmNT,
-                                                   c->lds_bytes) != hipSuccess || per_cu < 1) {
-    (void)hipGetLastError();
-    per_cu = 1;
-  }
-  c->max_grid = c->grid = (uint32_t)per_cu * (uint32_t)std::max(prop.multiProcessorCount, 1);
+  c->max_grid = c->grid = fmcw::resident_grid(emit, fmcw::kCmNT, c->lds_bytes, prop);
   const size_t ctl_words = 2 + 2 * (size_t)cfg->n_streams;
   if (hipMalloc(reinterpret_cast<void**>(&c->planes), 2 * c->plane_floats * sizeof(float)) != hipSuccess ||
       hipMalloc(reinterpret_cast<void**>(&c->ctl), ctl_words * sizeof(uint32_t)) != hipSuccess ||
@@ -186,7 +162,7 @@ int fmcw_cmap_create(const fmcw_cmap_config* cfg, fmcw_cmap** out) {
 
 int fmcw_cmap_set_grid_for_test(fmcw_cmap* c, uint32_t grid) {
   if (!c) return fail(FMCW_EINVAL, "null clutter map");
-  c->grid = grid ? std::min(c->max_grid, grid) : c->max_grid;
+  c->grid = fmcw::clamp_grid(grid, c->max_grid);
   return FMCW_OK;
 }
 
@@ -202,16 +178,15 @@ int fmcw_cmap_reset(fmcw_cmap* c, void* stream) {
 }
 
 static int state_copy(fmcw_cmap* c, bool set, float* planes_dev, uint32_t* ages_dev, void* stream) {
-  if (reinterpret_cast<uintptr_t>(planes_dev) & 15u) return fail(FMCW_EINVAL, "planes_dev must be 16-byte aligned");
-  if (reinterpret_cast<uintptr_t>(ages_dev) & 3u) return fail(FMCW_EINVAL, "ages_dev must be 4-byte aligned");
+  if (int rc = fmcw::aligned(planes_dev, 16, "planes_dev")) return rc;
+  if (int rc = fmcw::aligned(ages_dev, 4, "ages_dev")) return rc;
   if (hipSetDevice(c->cfg.device_id) != hipSuccess) return fail(FMCW_EHIP, "hipSetDevice");
   const size_t n4 = c->plane_floats / 4;
   const uint32_t blocks = planes_dev ? (uint32_t)std::min<size_t>((n4 + 255) / 256, 4096) : 1u;
   hipLaunchKernelGGL(set ? fmcw::k_cmap_state<true> : fmcw::k_cmap_state<false>, dim3(blocks), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), c->planes, c->ctl, planes_dev, ages_dev,
                      (int)c->cfg.n_streams, n4);
-  if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_cmap_state launch");
-  return FMCW_OK;
+  return fmcw::check_launch("k_cmap_state");
 }
 
 int fmcw_cmap_get_state(fmcw_cmap* c, float* planes_dev, uint32_t* ages_dev, void* stream) {
@@ -234,10 +209,7 @@ int fmcw_cmap_enqueue(fmcw_cmap* c, const float* map_dev, size_t n_frames, fmcw_
     return fail(FMCW_EINVAL, "n_frames %zu exceeds max_frames %u", n_frames, c->cfg.max_frames);
   if (n_frames % c->cfg.n_streams != 0)
     return fail(FMCW_EINVAL, "n_frames %zu is not a multiple of n_streams %u", n_frames, c->cfg.n_streams);
-  if (n_frames && !map_dev) return fail(FMCW_EINVAL, "null map_dev with n_frames %zu", n_frames);
-  if (reinterpret_cast<uintptr_t>(map_dev) & 15u) return fail(FMCW_EINVAL, "map_dev must be 16-byte aligned");
-  if (!dets_dev && det_cap) return fail(FMCW_EINVAL, "null dets_dev with det_cap %zu", det_cap);
-  if (reinterpret_cast<uintptr_t>(dets_dev) & 15u) return fail(FMCW_EINVAL, "dets_dev must be 16-byte aligned");
+  if (int rc = fmcw::check_map_and_dets(map_dev, n_frames, dets_dev, det_cap)) return rc;
   if (hipSetDevice(c->cfg.device_id) != hipSuccess) return fail(FMCW_EHIP, "hipSetDevice");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int n_scans = (int)(n_frames / c->cfg.n_streams);
@@ -252,16 +224,16 @@ int fmcw_cmap_enqueue(fmcw_cmap* c, const float* map_dev, size_t n_frames, fmcw_
     hipLaunchKernelGGL(c->count, dim3(n_wg), dim3(fmcw::kCmNT), c->lds_bytes, s, map_dev, c->planes,
                        static_cast<const uint32_t*>(c->ctl), c->args, n_scans, counts,
                        static_cast<const uint32_t*>(nullptr), static_cast<fmcw_det*>(nullptr), 0u);
-    if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_cmap count launch");
+    if (int rc = fmcw::check_launch("k_cmap count")) return rc;
   }
   hipLaunchKernelGGL(fmcw::k_cmap_scan, dim3(1), dim3(fmcw::kCmScanNT), 0, s, static_cast<const uint32_t*>(counts), offs,
                      n_tiles, n_dets_dev, c->ctl, (int)c->cfg.n_streams, (uint32_t)n_scans);
-  if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_cmap_scan launch");
+  if (int rc = fmcw::check_launch("k_cmap_scan")) return rc;
   if (n_scans) {   // whatever det_cap is: this pass also writes the state
     hipLaunchKernelGGL(c->emit, dim3(n_wg), dim3(fmcw::kCmNT), c->lds_bytes, s, map_dev, c->planes,
                        static_cast<const uint32_t*>(c->ctl), c->args, n_scans, static_cast<uint32_t*>(nullptr),
                        static_cast<const uint32_t*>(offs), dets_dev, cap);
-    if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_cmap emit launch");
+    if (int rc = fmcw::check_launch("k_cmap emit")) return rc;
   }
   return FMCW_OK;
 }

@@ -19,7 +19,8 @@
 // Three launches, no workgroup waits on another, no atomic and no counter that outlives a call:
 //   k_plots_find   peak test per detection (stops at the first larger neighbour): one 64-bit
 //                  ballot mask per 64 records, one peak count per tile
-//   k_plots_scan   one workgroup: exclusive scan of the tile counts, and the two status words
+//   k_plots_scan   one workgroup: exclusive scan of the tile counts (det_sink.hpp tile_offsets_scan,
+//                  the detectors' scan), and the two status words
 //   k_plots_emit   the peaks' rank from the tile offset and the masks; each peak below plot_cap
 //                  walks its window once more for the sums and writes its plot
 // Every word the later launches read is written by the earlier ones in the same call (tile counts
@@ -28,8 +29,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstring>
 
+#include "det_sink.hpp"
 #include "internal.hpp"
 #include "plots_window.hpp"
 
@@ -116,34 +117,12 @@ __global__ void __launch_bounds__(kThreads) k_plots_find(const fmcw_det* __restr
 __global__ void __launch_bounds__(kScanThreads) k_plots_scan(uint32_t cap, const uint32_t* __restrict__ n_dets,
                                                               uint32_t* __restrict__ tile_cnt,
                                                               uint32_t* __restrict__ n_plots) {
-  __shared__ uint32_t s_w[kScanThreads / 64];
   const uint32_t found = n_dets[0];
   const uint32_t n = min(found, cap);
-  const uint32_t n_tiles = (n + kTile - 1) / kTile;
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  uint32_t carry = 0;
-  for (uint32_t c0 = 0; c0 < n_tiles; c0 += kScanThreads) {
-    const uint32_t t = c0 + tid;
-    const uint32_t x = t < n_tiles ? tile_cnt[t] : 0u;
-    uint32_t incl = x;
-    for (int s = 1; s < 64; s <<= 1) {
-      const uint32_t y = __shfl_up(incl, s, 64);
-      if ((int)lane >= s) incl += y;
-    }
-    __syncthreads();  // the previous round's s_w readers are done
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-    for (uint32_t w = 0; w < kScanThreads / 64; ++w) {
-      const uint32_t sw = s_w[w];
-      if (w < wave) before += sw;
-      total += sw;
-    }
-    if (t < n_tiles) tile_cnt[t] = carry + before + incl - x;
-    carry += total;
-  }
-  if (tid == 0) {
-    n_plots[0] = carry;
+  const uint32_t n_tiles = (n + kTile - 1) / kTile;   // <= 2^21, a tile has at most kTile peaks
+  const uint32_t sum = fmcw::tile_offsets_scan<kScanThreads>(tile_cnt, tile_cnt, (int)n_tiles);
+  if (threadIdx.x == 0) {
+    n_plots[0] = sum;
     n_plots[1] = found - n;
   }
 }
@@ -208,7 +187,7 @@ int validate(const fmcw_plots_config& c) {
   if (c.n_doppler < 2 * c.win_doppler + 1 || c.n_doppler > 65536)
     return fail(FMCW_EINVAL, "n_doppler %u (2 win_doppler + 1 = %u .. 65536)", c.n_doppler, 2 * c.win_doppler + 1);
   if (c.max_dets < 1 || c.max_dets > 0x7fffffffu) return fail(FMCW_EINVAL, "max_dets %u (1..2^31-1)", c.max_dets);
-  if (c.device_id < 0 || c.device_id > 63) return fail(FMCW_EINVAL, "device_id %d (0..63)", c.device_id);
+  if (int rc = fmcw::check_device_id(c.device_id)) return rc;
   return FMCW_OK;
 }
 
@@ -237,21 +216,9 @@ void fmcw_plots_config_default(fmcw_plots_config* cfg) {
 int fmcw_plots_create(const fmcw_plots_config* cfg, fmcw_plotter** out) {
   if (!cfg || !out) return fail(FMCW_EINVAL, "null argument");
   *out = nullptr;
-  const int rc = validate(*cfg);
+  int rc = validate(*cfg);
   if (rc) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    (void)hipGetLastError();
-    return fail(FMCW_ENODEV, "no HIP device");
-  }
-  if (cfg->device_id >= ndev) return fail(FMCW_ENODEV, "device_id %d out of range", cfg->device_id);
-  hipDeviceProp_t prop;
-  if (hipSetDevice(cfg->device_id) != hipSuccess || hipGetDeviceProperties(&prop, cfg->device_id) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(FMCW_ENODEV, "device_id %d", cfg->device_id);
-  }
-  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(FMCW_ENODEV, "device %d is %s; this build targets gfx950 (MI355X)", cfg->device_id, prop.gcnArchName);
+  if ((rc = fmcw::open_device(cfg->device_id))) return rc;
   fmcw_plotter* p = new fmcw_plotter();
   p->cfg = *cfg;
   p->max_tiles = (uint32_t)(((uint64_t)cfg->max_dets + kTile - 1) / kTile);
@@ -278,7 +245,7 @@ int fmcw_plots_destroy(fmcw_plotter* p) {
 
 int fmcw_plots_set_grid_for_test(fmcw_plotter* p, uint32_t grid) {
   if (!p) return fail(FMCW_EINVAL, "null plotter");
-  p->grid = grid ? std::min(kMaxGrid, grid) : kMaxGrid;
+  p->grid = fmcw::clamp_grid(grid, kMaxGrid);
   return FMCW_OK;
 }
 
@@ -296,14 +263,14 @@ int fmcw_plots_enqueue(fmcw_plotter* p, const fmcw_det* dets_dev, size_t det_cap
   const dim3 grid(std::min(tiles, p->grid));
   if (tiles) {
     hipLaunchKernelGGL(k_plots_find, grid, dim3(kThreads), 0, s, dets_dev, cap, n_dets_dev, g, p->masks, p->tile_cnt);
-    if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_plots_find launch");
+    if (int rc = fmcw::check_launch("k_plots_find")) return rc;
   }
   hipLaunchKernelGGL(k_plots_scan, dim3(1), dim3(kScanThreads), 0, s, cap, n_dets_dev, p->tile_cnt, n_plots_dev);
-  if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_plots_scan launch");
+  if (int rc = fmcw::check_launch("k_plots_scan")) return rc;
   if (tiles && pcap) {
     hipLaunchKernelGGL(k_plots_emit, grid, dim3(kThreads), 0, s, dets_dev, cap, n_dets_dev, g, p->masks, p->tile_cnt,
                        plots_dev, pcap);
-    if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_plots_emit launch");
+    if (int rc = fmcw::check_launch("k_plots_emit")) return rc;
   }
   return FMCW_OK;
 }

@@ -10,7 +10,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstring>
 
 #include "internal.hpp"
 #include "tws_dev_kernel.hpp"
@@ -35,7 +34,7 @@ int validate(const fmcw_tws_dev_config& c) {
   if (c.n_streams < 1 || c.n_streams > 4096) return fail(FMCW_EINVAL, "n_streams %u (1..4096)", c.n_streams);
   if (c.max_scans < 1 || (uint64_t)c.max_scans * c.n_streams >= (1ull << 31))
     return fail(FMCW_EINVAL, "max_scans %u: need 1 <= max_scans and max_scans x n_streams < 2^31", c.max_scans);
-  if (c.device_id < 0 || c.device_id > 63) return fail(FMCW_EINVAL, "device_id %d (0..63)", c.device_id);
+  if (int rc = fmcw::check_device_id(c.device_id)) return rc;
   return FMCW_OK;
 }
 
@@ -61,21 +60,9 @@ void fmcw_tws_dev_config_default(fmcw_tws_dev_config* cfg) {
 int fmcw_tws_dev_create(const fmcw_tws_dev_config* cfg, fmcw_tws_dev** out) {
   if (!cfg || !out) return fail(FMCW_EINVAL, "null argument");
   *out = nullptr;
-  const int rc = validate(*cfg);
+  int rc = validate(*cfg);
   if (rc) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    (void)hipGetLastError();
-    return fail(FMCW_ENODEV, "no HIP device");
-  }
-  if (cfg->device_id >= ndev) return fail(FMCW_ENODEV, "device_id %d out of range", cfg->device_id);
-  hipDeviceProp_t prop;
-  if (hipSetDevice(cfg->device_id) != hipSuccess || hipGetDeviceProperties(&prop, cfg->device_id) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(FMCW_ENODEV, "device_id %d", cfg->device_id);
-  }
-  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(FMCW_ENODEV, "device %d is %s; this build targets gfx950 (MI355X)", cfg->device_id, prop.gcnArchName);
+  if ((rc = fmcw::open_device(cfg->device_id))) return rc;
   fmcw_tws_dev* t = new fmcw_tws_dev();
   t->cfg = *cfg;
   const size_t state_bytes = (size_t)cfg->n_streams * kStateWords * sizeof(uint32_t);
@@ -112,8 +99,7 @@ int fmcw_tws_dev_reset(fmcw_tws_dev* t, void* stream) {
   const uint32_t blocks = std::min<uint32_t>(1024u, (t->cfg.n_streams * kStateWords + 255u) / 256u);
   hipLaunchKernelGGL(k_tws_reset, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), t->state,
                      t->cfg.n_streams);
-  if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_tws_reset launch");
-  return FMCW_OK;
+  return fmcw::check_launch("k_tws_reset");
 }
 
 int fmcw_tws_dev_set_grid_for_test(fmcw_tws_dev* t, uint32_t grid) {
@@ -130,12 +116,12 @@ int fmcw_tws_dev_enqueue(fmcw_tws_dev* t, const void* recs_dev, size_t rec_strid
     return fail(FMCW_EINVAL, "rec_stride %zu (16: fmcw_det, 32: fmcw_plot)", rec_stride);
   if (track_cap < 1) return fail(FMCW_EINVAL, "track_cap %zu (>= 1)", track_cap);
   if (rec_cap && !recs_dev) return fail(FMCW_EINVAL, "null recs_dev with rec_cap %zu", rec_cap);
-  if (reinterpret_cast<uintptr_t>(recs_dev) & 3u) return fail(FMCW_EINVAL, "recs_dev must be 4-byte aligned");
+  if (int rc = fmcw::aligned(recs_dev, 4, "recs_dev")) return rc;
   if (!n_recs_dev) return fail(FMCW_EINVAL, "null n_recs_dev");
   if (!status_dev) return fail(FMCW_EINVAL, "null status_dev");
   if (n_scans && !tracks_dev) return fail(FMCW_EINVAL, "null tracks_dev with n_scans %zu", n_scans);
   if (n_scans && !counts_dev) return fail(FMCW_EINVAL, "null counts_dev with n_scans %zu", n_scans);
-  if (reinterpret_cast<uintptr_t>(tracks_dev) & 3u) return fail(FMCW_EINVAL, "tracks_dev must be 4-byte aligned");
+  if (int rc = fmcw::aligned(tracks_dev, 4, "tracks_dev")) return rc;
   if (!t) return fail(FMCW_EINVAL, "null tracker");
   if (n_scans > t->cfg.max_scans) return fail(FMCW_EINVAL, "n_scans %zu exceeds max_scans %u", n_scans, t->cfg.max_scans);
   if (hipSetDevice(t->cfg.device_id) != hipSuccess) return fail(FMCW_EHIP, "hipSetDevice");
@@ -145,18 +131,17 @@ int fmcw_tws_dev_enqueue(fmcw_tws_dev* t, const void* recs_dev, size_t rec_strid
   const uint32_t n_groups = (uint32_t)n_scans * n_streams;               // < 2^31 (validate)
   const uint8_t* recs = static_cast<const uint8_t*>(recs_dev);
   const uint32_t tiles = cap / kIdxTile + 1;
-  const uint32_t gi = std::min(tiles, t->grid ? std::min(t->grid, kIdxMaxGrid) : kIdxMaxGrid);
+  const uint32_t gi = std::min(tiles, fmcw::clamp_grid(t->grid, kIdxMaxGrid));
   hipLaunchKernelGGL(k_tws_index, dim3(gi), dim3(kIdxThreads), 0, s, recs, (uint32_t)rec_stride, cap, n_recs_dev,
                      n_groups, t->start);
-  if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_tws_index launch");
+  if (int rc = fmcw::check_launch("k_tws_index")) return rc;
   const uint32_t wgs = (n_streams + kTrackWaves - 1) / kTrackWaves;   // one wave per stream
-  const uint32_t gt = n_scans ? std::min(wgs, t->grid ? std::min(t->grid, kTrackMaxGrid) : kTrackMaxGrid) : 1u;
+  const uint32_t gt = n_scans ? std::min(wgs, fmcw::clamp_grid(t->grid, kTrackMaxGrid)) : 1u;
   auto track = t->cfg.tws.rtl_compat ? k_tws_track<true> : k_tws_track<false>;
   hipLaunchKernelGGL(track, dim3(gt), dim3(64 * kTrackWaves), 0, s, recs, (uint32_t)rec_stride, cap, n_recs_dev,
                      static_cast<const uint32_t*>(t->start), (uint32_t)n_scans, n_streams, t->cfg.tws, t->state,
                      reinterpret_cast<uint32_t*>(tracks_dev), track_cap, counts_dev, status_dev);
-  if (hipGetLastError() != hipSuccess) return fail(FMCW_EHIP, "k_tws_track launch");
-  return FMCW_OK;
+  return fmcw::check_launch("k_tws_track");
 }
 
 }  // extern "C"

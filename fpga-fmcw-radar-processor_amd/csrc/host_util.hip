@@ -1,0 +1,71 @@
+// host_util.hip -- the helpers of internal.hpp that the objects beside fmcw_handle share (plotter, bearing
+// estimator, beamformer, cell-averaging detector, device tracker, clutter map, adaptive weights).  Host
+// code only.
+#include <cstring>
+
+#include "internal.hpp"
+
+namespace fmcw {
+
+int check_map_dims(uint32_t n_range, uint32_t n_doppler) {
+  if (!pow2(n_range) || n_range < 64 || n_range > 8192)
+    return fail(FMCW_EINVAL, "n_range=%u: must be a power of two in [64, 8192]", n_range);
+  if (!pow2(n_doppler) || n_doppler < 32 || n_doppler > 1024)
+    return fail(FMCW_EINVAL, "n_doppler=%u: must be a power of two in [32, 1024]", n_doppler);
+  return FMCW_OK;
+}
+
+int check_device_id(int device_id) {
+  if (device_id < 0 || device_id > 63) return fail(FMCW_EINVAL, "device_id %d (0..63)", device_id);
+  return FMCW_OK;
+}
+
+int open_device(int device_id, hipDeviceProp_t* prop) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
+    (void)hipGetLastError();
+    return fail(FMCW_ENODEV, "no HIP device");
+  }
+  if (device_id >= ndev) return fail(FMCW_ENODEV, "device_id %d out of range", device_id);
+  hipDeviceProp_t p;
+  if (hipSetDevice(device_id) != hipSuccess || hipGetDeviceProperties(&p, device_id) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(FMCW_ENODEV, "device_id %d", device_id);
+  }
+  if (std::strncmp(p.gcnArchName, "gfx950", 6) != 0)
+    return fail(FMCW_ENODEV, "device %d is %s; this build targets gfx950 (MI355X)", device_id, p.gcnArchName);
+  if (prop) *prop = p;
+  return FMCW_OK;
+}
+
+int aligned(const void* p, unsigned bytes, const char* name) {
+  if (reinterpret_cast<uintptr_t>(p) & (bytes - 1u)) return fail(FMCW_EINVAL, "%s must be %u-byte aligned", name, bytes);
+  return FMCW_OK;
+}
+
+int check_map_and_dets(const float* map_dev, size_t n_frames, const fmcw_det* dets_dev, size_t det_cap) {
+  if (n_frames && !map_dev) return fail(FMCW_EINVAL, "null map_dev with n_frames %zu", n_frames);
+  if (int rc = aligned(map_dev, 16, "map_dev")) return rc;
+  if (!dets_dev && det_cap) return fail(FMCW_EINVAL, "null dets_dev with det_cap %zu", det_cap);
+  return aligned(dets_dev, 16, "dets_dev");
+}
+
+int raise_lds_limit(std::initializer_list<const void*> fns, size_t bytes, const char* name) {
+  for (const void* fn : fns)
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(FMCW_EHIP, "%s: %zu B of LDS per workgroup refused", name, bytes);
+    }
+  return FMCW_OK;
+}
+
+uint32_t resident_grid(const void* fn, int threads, size_t lds_bytes, const hipDeviceProp_t& prop) {
+  int per_cu = 1;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, lds_bytes) != hipSuccess || per_cu < 1) {
+    (void)hipGetLastError();
+    per_cu = 1;
+  }
+  return (uint32_t)per_cu * (uint32_t)std::max(prop.multiProcessorCount, 1);
+}
+
+}  // namespace fmcw

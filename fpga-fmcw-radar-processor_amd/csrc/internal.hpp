@@ -1,7 +1,11 @@
-// internal.hpp -- error plumbing shared by the host translation units of libfmcw.so.
+// internal.hpp -- what the host translation units of libfmcw.so share: the error plumbing (fmcw_api.hip)
+// and the helpers of the objects beside fmcw_handle (host_util.hip): device opening, argument checks,
+// grid sizing.  Free functions; every object keeps its own handle struct.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <initializer_list>
 #include <vector>
 
 #include "../../include/fmcw.h"
@@ -16,6 +20,31 @@ int check_launch(const char* what);
 // The fp32 window table of n points the kernels multiply by (fmcw_api.hip): FMCW_WIN_HAMMING, or
 // ones for FMCW_WIN_NONE, scaled by 2^-shift; FMCW_WIN_Q15_RTL gives the ROM integers.
 std::vector<float> window_table(uint32_t n, int kind, uint32_t shift = 0);
+
+inline bool pow2(uint32_t x) { return x && !(x & (x - 1)); }
+// a *_set_grid_for_test value against the built-in bound: 0 means the bound
+inline uint32_t clamp_grid(uint32_t grid, uint32_t max_grid) { return grid ? std::min(max_grid, grid) : max_grid; }
+
+// Every function below returns FMCW_OK, or the code of the fail() whose message it has set.
+
+// n_range a power of two in [64, 8192], n_doppler one in [32, 1024]: the maps the stage kernels write
+int check_map_dims(uint32_t n_range, uint32_t n_doppler);
+int check_device_id(int device_id);   // 0..63
+// Makes device_id (>= 0: check_device_id) the current device; FMCW_ENODEV unless it exists and is a
+// gfx950.  *prop, when given, receives its properties.
+int open_device(int device_id, hipDeviceProp_t* prop = nullptr);
+// "<name> must be <bytes>-byte aligned"; a null p passes
+int aligned(const void* p, unsigned bytes, const char* name);
+// What the detectors' enqueue ask of their map and their list, in this order: map_dev present (with
+// n_frames) and 16-byte aligned, dets_dev present (with det_cap) and 16-byte aligned.
+int check_map_and_dets(const float* map_dev, size_t n_frames, const fmcw_det* dets_dev, size_t det_cap);
+// hipFuncAttributeMaxDynamicSharedMemorySize = bytes on each kernel of `fns` ("<name>: .. refused").
+// The attribute is per kernel, not per object: pass the largest any configuration needs, so that it
+// does not shrink when a second object is created.
+int raise_lds_limit(std::initializer_list<const void*> fns, size_t bytes, const char* name);
+
+// Workgroups of `fn` resident at once: occupancy x CUs, 1 per CU where the runtime gives no answer.
+uint32_t resident_grid(const void* fn, int threads, size_t lds_bytes, const hipDeviceProp_t& prop);
 
 }  // namespace fmcw
 

@@ -9,8 +9,6 @@
 namespace fmcw {
 namespace {
 
-bool pow2(uint32_t x) { return x && !(x & (x - 1)); }
-
 // K2's FAST instantiation (doppler_kernel.hpp): MTI off, |X| magnitude, no dB map, fp32 windows, and the
 // 1-D CFAR (if any) at the reference geometry in fp32
 bool k2_fast(const fmcw_config& c) {
@@ -78,10 +76,7 @@ uint32_t chunk_frames(const fmcw_config& c, size_t frame_inter) {
 }  // namespace
 
 int validate(const fmcw_config& c) {
-  if (!pow2(c.n_range) || c.n_range < 64 || c.n_range > 8192)
-    return fail(FMCW_EINVAL, "n_range=%u: must be a power of two in [64, 8192]", c.n_range);
-  if (!pow2(c.n_doppler) || c.n_doppler < 32 || c.n_doppler > 1024)
-    return fail(FMCW_EINVAL, "n_doppler=%u: must be a power of two in [32, 1024]", c.n_doppler);
+  if (int rc = check_map_dims(c.n_range, c.n_doppler)) return rc;
   if (c.n_rx < 1 || c.n_rx > 64) return fail(FMCW_EINVAL, "n_rx=%u: must be in [1, 64]", c.n_rx);
   if (c.in_dtype < FMCW_IN_F32 || c.in_dtype > FMCW_IN_I16)
     return fail(FMCW_EINVAL, "in_dtype=%d unknown", c.in_dtype);

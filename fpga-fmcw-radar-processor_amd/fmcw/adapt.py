@@ -13,12 +13,11 @@ stream, capturable into a graph.  The reference is a single-channel core and has
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _lib as L
-from .radar_core import DeviceBuffer, _ptr
+from ._object import DeviceObject, ptr, stage
+from .radar_core import DeviceBuffer
 
 _MTI = {0: L.MTI_OFF, 2: L.MTI_2PULSE, 3: L.MTI_3PULSE}
 ADAPT_FALLBACK = 1       # FMCW_ADAPT_FALLBACK
@@ -41,29 +40,25 @@ def parse_info(words: np.ndarray) -> dict:
             "delta": float(w[4:6].copy().view(np.float64)[0]), "fallback": bool(int(w[2]) & ADAPT_FALLBACK)}
 
 
-class AdaptiveWeights:
+class AdaptiveWeights(DeviceObject):
+    _SYM = "fmcw_adapt"
+
     def __init__(self, N_RANGE: int, N_DOPPLER: int, N_RX: int, constraints, loading: float = 1e-2, mti: int = 0,
                  train_r0: int = 0, train_rows: int | None = None, device: int = 0):
         """constraints: complex [beam][rx], the array response a_b of each look direction
         (steering_vectors).  Training rows [train_r0, train_r0 + train_rows) (default: the whole map)."""
-        self._lib = L.load()
         a = np.ascontiguousarray(constraints, dtype=np.complex64)
         if a.ndim != 2 or a.shape[1] != N_RX:
             raise ValueError(f"constraints must be [beam][rx] with rx = {N_RX}, not {a.shape}")
-        cfg = L.FmcwAdaptConfig()
-        self._lib.fmcw_adapt_config_default(C.byref(cfg))
+        cfg = self._default_config(L.FmcwAdaptConfig)
         cfg.n_range, cfg.n_doppler, cfg.n_rx, cfg.n_beams = N_RANGE, N_DOPPLER, N_RX, a.shape[0]
         cfg.mti_mode = _MTI.get(mti, mti)
         cfg.train_r0 = train_r0
         cfg.train_rows = N_RANGE - train_r0 if train_rows is None else train_rows
         cfg.loading = loading
         cfg.device_id = device
-        self.cfg = cfg
-        self.device = device
         self.constraints = a
-        h = C.c_void_p()
-        L.check(self._lib.fmcw_adapt_create(C.byref(cfg), a.ctypes.data, C.byref(h)))
-        self._h = h
+        self._create(cfg, a.ctypes.data)
 
     @property
     def n_beams(self) -> int:
@@ -83,9 +78,8 @@ class AdaptiveWeights:
         """Asynchronous, device pointers only (DeviceBuffer / torch CUDA tensors / ints).  spec: n_frames
         frames of range_ct output; w: n_beams x n_rx complex64; cov: n_rx x n_rx complex128 or None;
         info: 8 uint32 words (parse_info)."""
-        def p(x):
-            return x if isinstance(x, int) or x is None else _ptr(x)[0]
-        L.check(self._lib.fmcw_adapt_enqueue(self._h, p(spec), n_frames, p(w), p(cov), p(info), stream or None))
+        L.check(self._lib.fmcw_adapt_enqueue(self._h, ptr(spec), n_frames, ptr(w), ptr(cov), ptr(info),
+                                             stream or None))
 
     def solve(self, spec):
         """Synchronous.  spec: range_ct output as a DeviceBuffer / CUDA tensor, or a host complex64
@@ -93,15 +87,7 @@ class AdaptiveWeights:
         c = self.cfg
         own = []
         try:
-            if isinstance(spec, np.ndarray):
-                host = np.ascontiguousarray(spec, dtype=np.complex64)
-                nbytes = host.nbytes
-                spec = DeviceBuffer(max(nbytes, 8), self.device)
-                own.append(spec)
-                if nbytes:
-                    spec.upload(host)
-            else:
-                nbytes = spec.nbytes if isinstance(spec, DeviceBuffer) else spec.numel() * spec.element_size()
+            spec, nbytes = stage(spec, np.complex64, 8, self.device, own)
             nf, rem = divmod(nbytes, self.spec_frame_bytes())
             if rem or nf == 0:
                 raise ValueError(f"spectrum of {nbytes} B is not a whole, positive number of frames "
@@ -119,21 +105,4 @@ class AdaptiveWeights:
     def set_grid_for_test(self, grid: int) -> None:
         """fmcw_adapt_set_grid_for_test: at most `grid` workgroups (0: the built-in bound), so that a
         small call drives a wave through several units."""
-        L.check(self._lib.fmcw_adapt_set_grid_for_test(self._h, int(grid)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.fmcw_adapt_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().set_grid_for_test(grid)

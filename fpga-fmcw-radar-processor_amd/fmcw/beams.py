@@ -10,12 +10,11 @@ so ``RadarCore.cfar`` runs on them as ``n_frames * n_beams`` frames; a detection
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _lib as L
-from .radar_core import DeviceBuffer, _ptr
+from ._object import DeviceObject, ptr, stage
+from .radar_core import DeviceBuffer
 
 _WINDOWS = {"hamming": L.WIN_HAMMING, "none": L.WIN_NONE}
 _MTI = {0: L.MTI_OFF, 2: L.MTI_2PULSE, 3: L.MTI_3PULSE}
@@ -35,27 +34,23 @@ def steering_weights(n_rx: int, nus, taper=None) -> np.ndarray:
     return (t * np.exp(-2j * np.pi * nus[:, None] * k[None, :]) / t.sum()).astype(np.complex64)
 
 
-class BeamFormer:
+class BeamFormer(DeviceObject):
+    _SYM = "fmcw_beams"
+
     def __init__(self, N_RANGE: int, N_DOPPLER: int, N_RX: int, weights, window: str = "hamming", mti: int = 0,
                  device: int = 0):
         """weights: complex [beam][rx] (steering_weights, or any matrix: taper and channel calibration
         are the caller's).  window: "hamming" or "none"; mti: 0 (off), 2 or 3 (pulse canceller)."""
-        self._lib = L.load()
         w = np.ascontiguousarray(weights, dtype=np.complex64)
         if w.ndim != 2 or w.shape[1] != N_RX:
             raise ValueError(f"weights must be [beam][rx] with rx = {N_RX}, not {w.shape}")
-        cfg = L.FmcwBeamsConfig()
-        self._lib.fmcw_beams_config_default(C.byref(cfg))
+        cfg = self._default_config(L.FmcwBeamsConfig)
         cfg.n_range, cfg.n_doppler, cfg.n_rx, cfg.n_beams = N_RANGE, N_DOPPLER, N_RX, w.shape[0]
         cfg.window = _WINDOWS[window] if isinstance(window, str) else window
         cfg.mti_mode = _MTI.get(mti, mti)
         cfg.device_id = device
-        self.cfg = cfg
-        self.device = device
         self.weights = w
-        h = C.c_void_p()
-        L.check(self._lib.fmcw_beams_create(C.byref(cfg), w.ctypes.data, C.byref(h)))
-        self._h = h
+        self._create(cfg, w.ctypes.data)
 
     @property
     def n_beams(self) -> int:
@@ -72,17 +67,14 @@ class BeamFormer:
     def enqueue(self, spec, n_frames: int, maps, stream: int = 0):
         """Asynchronous, device pointers only (DeviceBuffer / torch CUDA tensors / ints).  spec: n_frames
         frames of range_ct output; maps: room for n_frames * n_beams float32 maps, 16-byte aligned."""
-        def p(x):
-            return x if isinstance(x, int) or x is None else _ptr(x)[0]
-        L.check(self._lib.fmcw_beams_enqueue(self._h, p(spec), n_frames, p(maps), stream or None))
+        L.check(self._lib.fmcw_beams_enqueue(self._h, ptr(spec), n_frames, ptr(maps), stream or None))
 
     def set_weights_dev(self, w, stream: int = 0) -> None:
         """fmcw_beams_set_weights_dev: replace the matrix by n_beams x n_rx complex64 on the device
         (AdaptiveWeights.enqueue's w), stream-ordered and capturable.  Nothing checks the values:
         weights that are not finite give maps that are not finite.  `self.weights` keeps the matrix
         of the constructor."""
-        p = w if isinstance(w, int) else _ptr(w)[0]
-        L.check(self._lib.fmcw_beams_set_weights_dev(self._h, p, stream or None))
+        L.check(self._lib.fmcw_beams_set_weights_dev(self._h, ptr(w), stream or None))
 
     def form(self, spec) -> np.ndarray:
         """Synchronous.  spec: range_ct output as a DeviceBuffer / CUDA tensor, or a host complex64
@@ -90,15 +82,7 @@ class BeamFormer:
         c = self.cfg
         own = []
         try:
-            if isinstance(spec, np.ndarray):
-                host = np.ascontiguousarray(spec, dtype=np.complex64)
-                nbytes = host.nbytes
-                spec = DeviceBuffer(max(nbytes, 8), self.device)
-                own.append(spec)
-                if nbytes:
-                    spec.upload(host)
-            else:
-                nbytes = spec.nbytes if isinstance(spec, DeviceBuffer) else spec.numel() * spec.element_size()
+            spec, nbytes = stage(spec, np.complex64, 8, self.device, own)
             nf, rem = divmod(nbytes, self.spec_frame_bytes())
             if rem:
                 raise ValueError(f"spectrum of {nbytes} B is not a whole number of frames "
@@ -115,21 +99,4 @@ class BeamFormer:
     def set_grid_for_test(self, grid: int) -> None:
         """fmcw_beams_set_grid_for_test: at most `grid` workgroups (0: the built-in bound), so that a
         small call drives a workgroup through several tiles, frames and beams."""
-        L.check(self._lib.fmcw_beams_set_grid_for_test(self._h, int(grid)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.fmcw_beams_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().set_grid_for_test(grid)

@@ -15,8 +15,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from ._object import DeviceObject, ptr, stage
 from .plots import PLOT_DTYPE
-from .radar_core import DET_DTYPE, DeviceBuffer, _ptr
+from .radar_core import DET_DTYPE, DeviceBuffer
 
 BEARING_DTYPE = np.dtype([("frame", "<u4"), ("range", "<u2"), ("doppler", "<u2"), ("flags", "<u4"),
                           ("nu", "<f4"), ("sin_theta", "<f4"), ("power", "<f4"), ("coherence", "<f4"),
@@ -27,24 +28,20 @@ _WINDOWS = {"hamming": L.WIN_HAMMING, "none": L.WIN_NONE}
 _MTI = {0: L.MTI_OFF, 2: L.MTI_2PULSE, 3: L.MTI_3PULSE}
 
 
-class BearingEstimator:
+class BearingEstimator(DeviceObject):
+    _SYM = "fmcw_bearings"
+
     def __init__(self, N_RANGE: int = 1024, N_DOPPLER: int = 128, N_RX: int = 1, window: str = "hamming",
                  mti: int = 0, spacing: float = 0.5, max_records: int = 1 << 20, device: int = 0):
         """window: "hamming" or "none"; mti: 0 (off), 2 or 3 (pulse canceller) -- those of the
         RadarCore whose detections are located, so that ``power`` is the map's cell.  spacing: element
         spacing in wavelengths."""
-        self._lib = L.load()
-        cfg = L.FmcwBearingsConfig()
-        self._lib.fmcw_bearings_config_default(C.byref(cfg))
+        cfg = self._default_config(L.FmcwBearingsConfig)
         cfg.n_range, cfg.n_doppler, cfg.n_rx = N_RANGE, N_DOPPLER, N_RX
         cfg.window = _WINDOWS[window] if isinstance(window, str) else window
         cfg.mti_mode = _MTI.get(mti, mti)
         cfg.spacing, cfg.max_records, cfg.device_id = spacing, max_records, device
-        self.cfg = cfg
-        self.device = device
-        h = C.c_void_p()
-        L.check(self._lib.fmcw_bearings_create(C.byref(cfg), C.byref(h)))
-        self._h = h
+        self._create(cfg)
 
     def spec_frame_bytes(self) -> int:
         c = self.cfg
@@ -57,10 +54,9 @@ class BearingEstimator:
         n_records their device count word; bearings: room for min(rec_cap, max_records) records of
         BEARING_DTYPE; snaps: complex64 [record][rx] or None; n_out: FMCW_BEARING_STATUS_WORDS (2)
         uint32 device words: records processed, out-of-range records among them."""
-        def p(x):
-            return x if isinstance(x, int) or x is None else _ptr(x)[0]
-        L.check(self._lib.fmcw_bearings_enqueue(self._h, p(spec), n_frames, p(records), rec_stride, rec_cap,
-                                                p(n_records), p(bearings), p(snaps), p(n_out), stream or None))
+        L.check(self._lib.fmcw_bearings_enqueue(self._h, ptr(spec), n_frames, ptr(records), rec_stride, rec_cap,
+                                                ptr(n_records), ptr(bearings), ptr(snaps), ptr(n_out),
+                                                stream or None))
 
     def estimate(self, spec, records: np.ndarray, want_snaps: bool = True):
         """Synchronous.  spec: range_ct output as a DeviceBuffer / CUDA tensor, or a host complex64
@@ -74,15 +70,7 @@ class BearingEstimator:
             raise ValueError(f"{n} records exceed this estimator's max_records {self.cfg.max_records}")
         own = []
         try:
-            if isinstance(spec, np.ndarray):
-                host = np.ascontiguousarray(spec, dtype=np.complex64)
-                nbytes = host.nbytes
-                spec = DeviceBuffer(max(nbytes, 8), self.device)
-                own.append(spec)
-                if nbytes:
-                    spec.upload(host)
-            else:
-                nbytes = spec.nbytes if isinstance(spec, DeviceBuffer) else spec.numel() * spec.element_size()
+            spec, nbytes = stage(spec, np.complex64, 8, self.device, own)
             nf, rem = divmod(nbytes, self.spec_frame_bytes())
             if rem:
                 raise ValueError(f"spectrum of {nbytes} B is not a whole number of frames "
@@ -111,21 +99,4 @@ class BearingEstimator:
     def set_grid_for_test(self, grid: int) -> None:
         """fmcw_bearings_set_grid_for_test: at most `grid` workgroups (0: the built-in bound), so that
         a short list drives a workgroup through several records."""
-        L.check(self._lib.fmcw_bearings_set_grid_for_test(self._h, int(grid)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.fmcw_bearings_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().set_grid_for_test(grid)

@@ -12,19 +12,16 @@ in include/fmcw.h.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _lib as L
-from .radar_core import DET_DTYPE, DeviceBuffer, _ptr
+from ._object import DeviceObject, detect_maps, ptr
+from .radar_core import DeviceBuffer
 
 
-def _p(x):
-    return x if isinstance(x, int) or x is None else _ptr(x)[0]
+class ClutterMap(DeviceObject):
+    _SYM = "fmcw_cmap"
 
-
-class ClutterMap:
     def __init__(self, N_RANGE: int = 1024, N_DOPPLER: int = 128, n_streams: int = 1, gain: float = 0.125,
                  alpha: float = 4.0, floor: float = 0.0, clip: float = 0.0, spread=(1, 1), warmup: int = 8,
                  max_frames: int = 1, device: int = 0):
@@ -33,18 +30,12 @@ class ClutterMap:
         input may exceed its average by (a factor) when it enters the average.  spread: (range, doppler)
         half extents, 0..4, of the neighbourhood whose largest average sets the threshold.  warmup: scans
         a stream must have seen before it detects."""
-        self._lib = L.load()
-        cfg = L.FmcwCmapConfig()
-        self._lib.fmcw_cmap_config_default(C.byref(cfg))
+        cfg = self._default_config(L.FmcwCmapConfig)
         cfg.n_range, cfg.n_doppler, cfg.n_streams = N_RANGE, N_DOPPLER, n_streams
         cfg.gain, cfg.alpha, cfg.floor, cfg.clip = gain, alpha, floor, clip
         cfg.spread_range, cfg.spread_doppler = spread
         cfg.warmup, cfg.max_frames, cfg.device_id = warmup, max_frames, device
-        self.cfg = cfg
-        self.device = device
-        h = C.c_void_p()
-        L.check(self._lib.fmcw_cmap_create(C.byref(cfg), C.byref(h)))
-        self._h = h
+        self._create(cfg)
 
     def map_frame_bytes(self) -> int:
         return self.cfg.n_range * self.cfg.n_doppler * 4
@@ -58,7 +49,8 @@ class ClutterMap:
         float32 maps, n_frames a multiple of n_streams; dets: room for det_cap records (None with det_cap
         0); n_dets: FMCW_STATUS_WORDS (4) uint32 device words, [0] = detections found (may exceed
         det_cap).  The state advances by n_frames / n_streams scans whatever det_cap is."""
-        L.check(self._lib.fmcw_cmap_enqueue(self._h, _p(maps), n_frames, _p(dets), det_cap, _p(n_dets), stream or None))
+        L.check(self._lib.fmcw_cmap_enqueue(self._h, ptr(maps), n_frames, ptr(dets), det_cap, ptr(n_dets),
+                                            stream or None))
 
     def reset(self, stream: int = 0) -> None:
         """Every stream's age goes to 0, in stream order: the next scan initialises the map."""
@@ -68,7 +60,7 @@ class ClutterMap:
         """With device pointers: a stream-ordered copy of the n_streams planes and / or age words into
         them.  With neither: synchronous, returns (planes float32 [stream][range][doppler], ages uint32)."""
         if planes is not None or ages is not None:
-            L.check(self._lib.fmcw_cmap_get_state(self._h, _p(planes), _p(ages), stream or None))
+            L.check(self._lib.fmcw_cmap_get_state(self._h, ptr(planes), ptr(ages), stream or None))
             return None
         pb, ab = self.state_bytes()
         dp, da = DeviceBuffer(pb, self.device), DeviceBuffer(max(ab, 16), self.device)
@@ -100,7 +92,7 @@ class ClutterMap:
                 ages = DeviceBuffer(max(host.nbytes, 16), self.device)
                 own.append(ages)
                 ages.upload(host)
-            L.check(self._lib.fmcw_cmap_set_state(self._h, _p(planes), _p(ages), stream or None))
+            L.check(self._lib.fmcw_cmap_set_state(self._h, ptr(planes), ptr(ages), stream or None))
             if own:
                 own[0].download(np.uint8, (1,))   # synchronous: the copy is done before the staging buffers go
         finally:
@@ -112,62 +104,18 @@ class ClutterMap:
         DeviceBuffer / CUDA tensor holding whole maps.  Returns the DET_DTYPE list and advances the state
         by the call's scans, once: a rerun would advance it twice, so the state is saved before the call
         and restored before the single rerun when the first capacity was short."""
-        own = []
+        pb, ab = self.state_bytes()
+        sp, sa = DeviceBuffer(pb, self.device), DeviceBuffer(max(ab, 16), self.device)
         try:
-            if isinstance(maps, np.ndarray):
-                host = np.ascontiguousarray(maps, dtype=np.float32)
-                nbytes = host.nbytes
-                maps = DeviceBuffer(max(nbytes, 16), self.device)
-                own.append(maps)
-                if nbytes:
-                    maps.upload(host)
-            else:
-                nbytes = maps.nbytes if isinstance(maps, DeviceBuffer) else maps.numel() * maps.element_size()
-            nf, rem = divmod(nbytes, self.map_frame_bytes())
-            if rem:
-                raise ValueError(f"maps of {nbytes} B are not a whole number of frames ({self.map_frame_bytes()} B each)")
-            cap = max(nf * 4096, 64) if det_cap is None else det_cap
-            dn = DeviceBuffer(4 * L.STATUS_WORDS, self.device)
-            pb, ab = self.state_bytes()
-            sp, sa = DeviceBuffer(pb, self.device), DeviceBuffer(max(ab, 16), self.device)
-            own += [dn, sp, sa]
             self.get_state(sp, sa)
-            for attempt in range(2):
-                dd = DeviceBuffer(max(cap, 1) * DET_DTYPE.itemsize, self.device)
-                try:
-                    self.enqueue(maps, nf, dd, cap, dn)
-                    # fmcw_memcpy is synchronous on the default stream the call ran on
-                    found = int(dn.download(np.uint32, (L.STATUS_WORDS,))[0])
-                    if found <= cap:
-                        return dd.download(DET_DTYPE, (found,))
-                finally:
-                    dd.free()
-                if attempt == 0:
-                    self.set_state(sp, sa)
-                cap = found
-            raise RuntimeError("detection count changed between two runs on the same maps and state")
+            return detect_maps(self, maps, det_cap,
+                               "detection count changed between two runs on the same maps and state",
+                               before_rerun=lambda: self.set_state(sp, sa))
         finally:
-            for b in own:
-                b.free()
+            sp.free()
+            sa.free()
 
     def set_grid_for_test(self, grid: int) -> None:
         """fmcw_cmap_set_grid_for_test: at most `grid` workgroups for the two passes (0: the built-in
         bound), so that a small call drives a workgroup through several (stream, tile) units."""
-        L.check(self._lib.fmcw_cmap_set_grid_for_test(self._h, int(grid)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.fmcw_cmap_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().set_grid_for_test(grid)

@@ -16,7 +16,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .radar_core import DET_DTYPE, DeviceBuffer, _ptr
+from ._object import DeviceObject, ptr
+from .radar_core import DET_DTYPE, DeviceBuffer
 
 PLOT_DTYPE = np.dtype([("frame", "<u4"), ("range", "<u2"), ("doppler", "<u2"), ("mag", "<f4"),
                        ("threshold", "<f4"), ("n_cells", "<u4"), ("sum_mag", "<f4"),
@@ -24,29 +25,23 @@ PLOT_DTYPE = np.dtype([("frame", "<u4"), ("range", "<u2"), ("doppler", "<u2"), (
 assert PLOT_DTYPE.itemsize == C.sizeof(L.FmcwPlot) == 32
 
 
-class PlotExtractor:
+class PlotExtractor(DeviceObject):
+    _SYM = "fmcw_plots"
+
     def __init__(self, N_RANGE: int = 1024, N_DOPPLER: int = 128, win=(1, 1), max_dets: int = 1 << 20,
                  device: int = 0):
-        self._lib = L.load()
-        cfg = L.FmcwPlotsConfig()
-        self._lib.fmcw_plots_config_default(C.byref(cfg))
+        cfg = self._default_config(L.FmcwPlotsConfig)
         cfg.n_range, cfg.n_doppler = N_RANGE, N_DOPPLER
         cfg.win_range, cfg.win_doppler = win
         cfg.max_dets, cfg.device_id = max_dets, device
-        self.cfg = cfg
-        self.device = device
-        h = C.c_void_p()
-        L.check(self._lib.fmcw_plots_create(C.byref(cfg), C.byref(h)))
-        self._h = h
+        self._create(cfg)
 
     def enqueue(self, dets, det_cap: int, n_dets, plots, plot_cap: int, n_plots, stream: int = 0):
         """Asynchronous, device pointers only (DeviceBuffer / torch CUDA tensors / ints).  dets and
         n_dets as fmcw_enqueue wrote them; n_plots: FMCW_PLOT_STATUS_WORDS (2) uint32 device words:
         plots found (may exceed plot_cap), records not examined."""
-        def p(x):
-            return x if isinstance(x, int) or x is None else _ptr(x)[0]
-        L.check(self._lib.fmcw_plots_enqueue(self._h, p(dets), det_cap, p(n_dets), p(plots), plot_cap,
-                                             p(n_plots), stream or None))
+        L.check(self._lib.fmcw_plots_enqueue(self._h, ptr(dets), det_cap, ptr(n_dets), ptr(plots),
+                                             plot_cap, ptr(n_plots), stream or None))
 
     def extract(self, dets: np.ndarray, plot_cap: int | None = None) -> np.ndarray:
         """Synchronous: a host DET_DTYPE array (sorted by frame, range, doppler) -> host PLOT_DTYPE
@@ -83,21 +78,4 @@ class PlotExtractor:
     def set_grid_for_test(self, grid: int) -> None:
         """fmcw_plots_set_grid_for_test: at most `grid` workgroups for the two tile kernels (0: the
         built-in bound), so that a short list drives a workgroup through several tiles."""
-        L.check(self._lib.fmcw_plots_set_grid_for_test(self._h, int(grid)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.fmcw_plots_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().set_grid_for_test(grid)

@@ -15,30 +15,27 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from ._object import DeviceObject, ptr
 from .plots import PLOT_DTYPE
-from .radar_core import DET_DTYPE, DeviceBuffer, _ptr
+from .radar_core import DET_DTYPE, DeviceBuffer
 from .tracker import TRACK_DTYPE
 
 assert TRACK_DTYPE.itemsize == C.sizeof(L.FmcwTrack) == 28
 
 
-class DeviceTwsTracker:
+class DeviceTwsTracker(DeviceObject):
+    _SYM = "fmcw_tws_dev"
+
     def __init__(self, n_streams: int = 1, max_scans: int = 1024, device: int = 0, MAX_TRACKS: int = 32,
                  INIT_HITS: int = 2, COAST_MAX: int = 5, ASSOC_GATE_R: int = 10, ASSOC_GATE_D: int = 5,
                  ALPHA_GAIN: int = 128, BETA_GAIN: int = 64, MAX_DETS: int = 64, rtl_compat: bool = False):
-        self._lib = L.load()
-        cfg = L.FmcwTwsDevConfig()
-        self._lib.fmcw_tws_dev_config_default(C.byref(cfg))
+        cfg = self._default_config(L.FmcwTwsDevConfig)
         t = cfg.tws
         t.max_tracks, t.max_dets, t.init_hits, t.coast_max = MAX_TRACKS, MAX_DETS, INIT_HITS, COAST_MAX
         t.gate_r, t.gate_d, t.alpha_q8, t.beta_q8 = ASSOC_GATE_R, ASSOC_GATE_D, ALPHA_GAIN, BETA_GAIN
         t.rtl_compat = int(bool(rtl_compat))
         cfg.n_streams, cfg.max_scans, cfg.device_id = n_streams, max_scans, device
-        self.cfg = cfg
-        self.device = device
-        h = C.c_void_p()
-        L.check(self._lib.fmcw_tws_dev_create(C.byref(cfg), C.byref(h)))
-        self._h = h
+        self._create(cfg)
 
     def enqueue(self, recs, rec_stride: int, rec_cap: int, n_recs, n_scans: int, tracks, track_cap: int,
                 counts, status, stream: int = 0):
@@ -47,10 +44,9 @@ class DeviceTwsTracker:
         n_scans x n_streams x track_cap TRACK_DTYPE records; counts: 2 words per (scan, stream)
         (tracks reported, active tracks); status: FMCW_TWS_DEV_STATUS_WORDS (2) words (records not
         examined, examined records at or beyond frame n_scans x n_streams)."""
-        def p(x):
-            return x if isinstance(x, int) or x is None else _ptr(x)[0]
-        L.check(self._lib.fmcw_tws_dev_enqueue(self._h, p(recs), rec_stride, rec_cap, p(n_recs), n_scans,
-                                               p(tracks), track_cap, p(counts), p(status), stream or None))
+        L.check(self._lib.fmcw_tws_dev_enqueue(self._h, ptr(recs), rec_stride, rec_cap, ptr(n_recs), n_scans,
+                                               ptr(tracks), track_cap, ptr(counts), ptr(status),
+                                               stream or None))
 
     def run(self, records: np.ndarray, n_scans: int):
         """Synchronous: a host DET_DTYPE or PLOT_DTYPE array with non-decreasing frames -> a list over
@@ -91,21 +87,4 @@ class DeviceTwsTracker:
         """fmcw_tws_dev_set_grid_for_test: at most `grid` workgroups for both kernels (0: the built-in
         bound), so that a short list drives the index kernel through several tiles and one wave of
         the tracker through several streams."""
-        L.check(self._lib.fmcw_tws_dev_set_grid_for_test(self._h, int(grid)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.fmcw_tws_dev_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().set_grid_for_test(grid)

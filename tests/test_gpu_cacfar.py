@@ -166,6 +166,34 @@ def test_persistent_loops_with_several_tiles_per_frame(gpu):
             assert st.tolist() == [len(want), 0, 0, 0] and got.tobytes() == want.tobytes(), grid
 
 
+def scan_rounds_maps():
+    """1025 frames of 64 x 32 (one tile per frame): Rayleigh noise and 1 + f % 7 cells of 60 in frame f,
+    6 rows apart (outside each other's window of +-5 rows), so that no tile is empty and the counts
+    differ from tile to tile."""
+    nf, nr, nd = 1025, 64, 32
+    maps = np.random.default_rng(51).rayleigh(1.0, (nf, nr, nd)).astype(np.float32)
+    for f in range(nf):
+        for j in range(1 + f % 7):
+            maps[f, 8 + 6 * j, (5 * j + f) % nd] = 60.0
+    return maps
+
+
+def test_scan_beyond_its_first_round(gpu):
+    """1025 tiles: k_cacfar_scan (det_sink.hpp tile_offsets_scan) takes a second round of 1024 tiles, and
+    tile 1024's offset is the first round's total.  Unequal, non-zero counts per tile: a wrong carry or
+    offset moves records.  The built-in grid, and 3 workgroups, each reading offsets of both rounds."""
+    maps = scan_rounds_maps()
+    nf, nr, nd = maps.shape
+    want = R.detect(maps)
+    per_tile = np.bincount(want["frame"], minlength=nf)          # one tile per frame at 64 x 32
+    assert len(per_tile) == 1025 and per_tile.min() >= 1 and len(set(per_tile.tolist())) > 1
+    with CaCfar(nr, nd, max_frames=nf) as det:
+        for grid in (0, 3):
+            det.set_grid_for_test(grid)
+            got, st = run(det, maps, det_cap=len(want) + 8)
+            assert st.tolist() == [len(want), 0, 0, 0] and got.tobytes() == want.tobytes(), grid
+
+
 def test_input_conventions(gpu):
     """Negative cells and -0.0 enter as +0; +Inf cells follow IEEE arithmetic: the reference on the
     same map (which clamps as the header says)."""

@@ -215,6 +215,38 @@ def test_persistent_loops(gpu, nd):
             same_state(cm, planes, ages)
 
 
+def scan_rounds_maps():
+    """129 scans of 64 x 1024 (8 tiles of 8 rows per plane, 1032 tiles): Rayleigh noise, and from scan 1 on
+    1 + (f + 3 t) % 5 cells of 1000 in tile t of scan f, at cells that move with f, so that every tile
+    after the first scan detects and the counts differ from tile to tile."""
+    nf, nr, nd = 129, 64, 1024
+    maps = np.random.default_rng(61).rayleigh(1.0, (nf, nr, nd)).astype(np.float32)
+    for f in range(1, nf):
+        for t in range(8):
+            for j in range(1 + (f + 3 * t) % 5):
+                maps[f, 8 * t + 1 + j, (37 * f + 101 * j + 7 * t) % nd] = 1000.0
+    return maps
+
+
+def test_scan_beyond_its_first_round(gpu):
+    """1032 tiles: k_cmap_scan (det_sink.hpp tile_offsets_scan) takes a second round of 1024 tiles, and
+    tile 1024's offset is the first round's total.  Per-tile counts unequal and, past the first scan
+    (age 0 detects nothing), non-zero: a wrong carry or offset moves records.  The built-in grid, and 3
+    workgroups, each reading offsets of both rounds."""
+    maps = scan_rounds_maps()
+    nf, nr, nd = maps.shape
+    kw = dict(warmup=1)
+    want, planes, ages = R.detect(maps, **kw)
+    per_tile = np.bincount(want["frame"].astype(np.int64) * 8 + want["range"] // 8, minlength=nf * 8)
+    assert len(per_tile) == 1032 and per_tile[8:].min() >= 1 and len(set(per_tile[8:].tolist())) > 1
+    for grid in (0, 3):
+        with ClutterMap(nr, nd, max_frames=nf, **kw) as cm:
+            cm.set_grid_for_test(grid)
+            got, st = run(cm, maps, det_cap=len(want) + 8)
+            assert st.tolist() == [len(want), 0, 0, 0] and got.tobytes() == want.tobytes(), grid
+            same_state(cm, planes, ages)
+
+
 def test_capacity(gpu):
     """det_cap at half the count, then 0 with a NULL list: the first records only, the full count, and
     the state advancing as if nothing were short.  ClutterMap.detect with a short first capacity returns

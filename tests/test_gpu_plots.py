@@ -199,6 +199,48 @@ def test_capped_grid_plot_cap_shorter_than_count(gpu):
             assert_plots_match(px.extract(dets, plot_cap=cap), want)
 
 
+def scan_rounds_list():
+    """The first 1024 * 1024 + 1 cells (1025 tiles) of 20 frames of 1024 x 128 filled at a density that
+    changes with the frame (0.30 .. 0.65), in (frame, range, doppler) order, no cell twice.  Magnitudes
+    from {1..5} (the last record: 9): ties everywhere, the peak counts differ from tile to tile, and
+    every sum of at most 9 of them, times an offset of at most 1, is exact in fp32 in any order."""
+    nf, nr, nd, n = 20, 1024, 128, 1024 * 1024 + 1
+    rng = np.random.default_rng(71)
+    density = 0.30 + 0.05 * (np.arange(nf) % 8)
+    f, r, d = np.nonzero(rng.random((nf, nr, nd)) < density[:, None, None])
+    assert len(f) >= n
+    a = np.zeros(n, DET_DTYPE)
+    a["frame"], a["range"], a["doppler"] = f[:n], r[:n], d[:n]
+    a["mag"] = rng.integers(1, 6, n).astype(np.float32)
+    a["mag"][-1] = 9.0             # the one record of tile 1024 is a peak
+    a["threshold"] = rng.random(n).astype(np.float32)
+    return a, nr, nd
+
+
+def test_scan_beyond_its_first_round(gpu):
+    """1025 tiles: k_plots_scan (det_sink.hpp tile_offsets_scan, in place on the tile counts) takes a
+    second round of 1024 tiles, and tile 1024's offset is the first round's total.  Unequal, non-zero
+    peak counts per tile: a wrong carry or offset moves plots.  The built-in grid, and 3 workgroups,
+    each reading offsets of both rounds.  With this list's small integer magnitudes the fp32 sums are
+    exact and d_range / d_doppler are one correctly rounded division, so beyond assert_plots_match
+    every field equals the reference's rounded to fp32."""
+    dets, nr, nd = scan_rounds_list()
+    n = len(dets)
+    want = plots_ref(dets, nr, nd, 1, 1)
+    key = lambda a: (a["frame"].astype(np.int64) * nr + a["range"]) * nd + a["doppler"]
+    per_tile = np.bincount(np.searchsorted(key(dets), key(want)) // 1024, minlength=1025)
+    assert len(per_tile) == 1025 and per_tile.min() >= 1 and len(set(per_tile.tolist())) > 1
+    with PlotExtractor(nr, nd, win=(1, 1), max_dets=n) as px:
+        for grid in (0, 3):
+            px.set_grid_for_test(grid)
+            st, got, rest = run(px, dets, plot_cap=len(want) + 4)
+            assert list(st) == [len(want), 0], grid
+            assert_plots_match(got, want)
+            for name in ("sum_mag", "d_range", "d_doppler"):
+                np.testing.assert_array_equal(got[name], want[name].astype(np.float32), err_msg=f"{name}, grid {grid}")
+            assert np.all(rest == SENTINEL)
+
+
 def test_truncated_input(gpu):
     """n_dets_dev[0] above det_cap, and above max_dets: the first n records are examined, word [1]
     counts the rest, and the plots equal the reference on the truncated list."""
