@@ -44,6 +44,7 @@ PLOT_STATUS_WORDS = 2  # FMCW_PLOT_STATUS_WORDS: n_plots_dev = plots found, reco
 BEARING_STATUS_WORDS = 2  # FMCW_BEARING_STATUS_WORDS: n_out_dev = records processed, out of range
 CACFAR_CA, CACFAR_GO, CACFAR_SO = 0, 1, 2   # fmcw_cacfar_mode
 TWS_DEV_STATUS_WORDS = 2  # FMCW_TWS_DEV_STATUS_WORDS: status_dev = records not examined, out of range
+MERGE_STATUS_WORDS = 3   # FMCW_MERGE_STATUS_WORDS: status_dev = merged plots found, records not examined, out of range
 BEARING_NO_ANGLE, BEARING_ONE_RX, BEARING_OUT_OF_RANGE = 1, 2, 4   # fmcw_bearing.flags bits
 
 STATUS_NAMES = {0: "FMCW_OK", -1: "FMCW_EINVAL", -2: "FMCW_ENOMEM", -3: "FMCW_EHIP",
@@ -82,6 +83,20 @@ class FmcwPlot(C.Structure):
 class FmcwPlotsConfig(C.Structure):
     _fields_ = [("n_range", C.c_uint32), ("n_doppler", C.c_uint32), ("win_range", C.c_uint32),
                 ("win_doppler", C.c_uint32), ("max_dets", C.c_uint32), ("device_id", C.c_int32)]
+
+
+class FmcwMplot(C.Structure):
+    _fields_ = [("frame", C.c_uint32), ("range", C.c_uint16), ("doppler", C.c_uint16),
+                ("mag", C.c_float), ("beam", C.c_uint16), ("n_merged", C.c_uint16),
+                ("sum_mag", C.c_float), ("d_beam", C.c_float), ("d_range", C.c_float),
+                ("d_doppler", C.c_float)]
+
+
+class FmcwMergeConfig(C.Structure):
+    _fields_ = [("n_range", C.c_uint32), ("n_doppler", C.c_uint32), ("n_beams", C.c_uint32),
+                ("win_beam", C.c_uint32), ("win_range", C.c_uint32), ("win_doppler", C.c_uint32),
+                ("beam_wrap", C.c_uint32), ("max_recs", C.c_uint32), ("max_maps", C.c_uint32),
+                ("device_id", C.c_int32)]
 
 
 class FmcwBearing(C.Structure):
@@ -177,6 +192,11 @@ SIGNATURES = {
     "fmcw_plots_destroy": (_I, [_VP]),
     "fmcw_plots_enqueue": (_I, [_VP, _VP, _SZ, _VP, _VP, _SZ, _VP, _VP]),
     "fmcw_plots_set_grid_for_test": (_I, [_VP, C.c_uint32]),
+    "fmcw_merge_config_default": (None, [C.POINTER(FmcwMergeConfig)]),
+    "fmcw_merge_create": (_I, [C.POINTER(FmcwMergeConfig), C.POINTER(_VP)]),
+    "fmcw_merge_destroy": (_I, [_VP]),
+    "fmcw_merge_enqueue": (_I, [_VP, _VP, _SZ, _SZ, _VP, _SZ, _VP, _SZ, _VP, _VP]),
+    "fmcw_merge_set_grid_for_test": (_I, [_VP, C.c_uint32]),
     "fmcw_bearings_config_default": (None, [C.POINTER(FmcwBearingsConfig)]),
     "fmcw_bearings_create": (_I, [C.POINTER(FmcwBearingsConfig), C.POINTER(_VP)]),
     "fmcw_bearings_destroy": (_I, [_VP]),

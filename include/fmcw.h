@@ -100,7 +100,10 @@ extern "C" {
                                and types of its own, nothing existing changes.
                                Still 8 with the adaptive beam weights (fmcw_adapt_*, fmcw_adapt_config)
                                and fmcw_beams_set_weights_dev: functions and types of their own; a
-                               beamformer that never calls the new function behaves as before */
+                               beamformer that never calls the new function behaves as before.
+                               Still 8 with the beam merge (fmcw_merge_*, fmcw_mplot,
+                               fmcw_merge_config): functions and types of its own, nothing
+                               existing changes */
 
 typedef enum {
   FMCW_OK = 0,
@@ -443,6 +446,82 @@ int fmcw_plots_enqueue(fmcw_plotter* p, const fmcw_det* dets_dev, size_t det_cap
  * over the 1024-record tiles, so that a short list drives a workgroup through several tiles.
  * 0 = the built-in bound (4096), else min(that bound, grid).  Plots never depend on it. */
 int fmcw_plots_set_grid_for_test(fmcw_plotter* p, uint32_t grid);
+
+/* ---- Beam merge: one report per target across the beams of a scan, with beam position ----
+ * After the beamformer the chain runs on n_frames * n_beams maps, and a record's .frame is
+ * m = f * n_beams + b (scan f, beam b).  Neighbouring beams overlap, so one target gives a plot in
+ * every beam that sees it.  The merger is the plot extractor's peak grouping with the beam as a
+ * third axis: a record list in, one fmcw_mplot per local maximum over (beam, range, Doppler) out,
+ * on the device, from the list alone.  It is an object of its own, not part of fmcw_handle.
+ *
+ * Input: a record list and its count word.  A record begins {uint32 frame; uint16 range; uint16
+ * doppler; float mag}; the stride is 16 (fmcw_det) or 32 (fmcw_plot).  Records are strictly
+ * increasing in (frame, range, doppler), range < n_range, doppler < n_doppler.  Record frame m is
+ * scan f = m / n_beams, beam b = m % n_beams.
+ * The neighbourhood of P = (f, b, r, d) is every record (f, b + db, r + dr, (d + dd) mod n_doppler),
+ * P included, with |db| <= win_beam, |dr| <= win_range, |dd| <= win_doppler and 0 <= r + dr <
+ * n_range; the beam axis is clamped (0 <= b + db < n_beams) when beam_wrap == 0 and circular
+ * ((b + db) mod n_beams; DFT beams, whose u axis wraps) when beam_wrap == 1, which requires
+ * n_beams >= 2 win_beam + 1.  Doppler is circular, range is clamped.  P is a peak iff for every
+ * other Q of its neighbourhood mag(P) > mag(Q), or mag(P) == mag(Q) and P precedes Q in the list.
+ * Every peak gives one merged plot, in list order of the peaks, so the output's .frame (the scan)
+ * is non-decreasing, as the device tracker requires.  NaN magnitudes are outside the
+ * specification. */
+typedef struct fmcw_mplot {   /* 32 bytes: fmcw_tws_dev_enqueue and fmcw_bearings_enqueue take it at stride 32 */
+  uint32_t frame;            /* the scan f (not f * n_beams + b) */
+  uint16_t range;            /* the peak record's cell */
+  uint16_t doppler;
+  float mag;                 /* the peak record's mag, bit for bit */
+  uint16_t beam;             /* the peak's beam */
+  uint16_t n_merged;         /* records in the neighbourhood, the peak included (<= 729) */
+  float sum_mag;             /* S = sum of their mag (fp32; ascending db, then dr, then the column runs) */
+  float d_beam;              /* sum(mag * db) / S: offsets from the peak in beams / bins; on a wrapped */
+  float d_range;             /* sum(mag * dr) / S  beam axis db is the signed offset in [-win_beam,    */
+  float d_doppler;           /* sum(mag * dd) / S  win_beam]; |.| <= win; all 0 if S is 0 or not finite */
+} fmcw_mplot;
+typedef struct fmcw_merge_config {   /* 10 words, 40 bytes */
+  uint32_t n_range;          /* 1..65536 */
+  uint32_t n_doppler;        /* 2 win_doppler + 1 .. 65536 */
+  uint32_t n_beams;          /* 1..64 */
+  uint32_t win_beam;         /* 0..4 */
+  uint32_t win_range;        /* 0..4 */
+  uint32_t win_doppler;      /* 0..4 */
+  uint32_t beam_wrap;        /* 0: beam axis clamped; 1: circular (n_beams >= 2 win_beam + 1) */
+  uint32_t max_recs;         /* most records one call examines, 1..2^31-1; scratch: 1 bit per record
+                                and 4 B per 1024 records */
+  uint32_t max_maps;         /* most maps (scans * n_beams) one call covers: >= n_beams, a multiple of
+                                it, < 2^31; scratch: 4 B per map */
+  int32_t device_id;         /* 0..63 */
+} fmcw_merge_config;
+typedef struct fmcw_merger fmcw_merger;
+/* Status words of fmcw_merge_enqueue (status_dev). */
+#define FMCW_MERGE_STATUS_WORDS 3
+/* Defaults: 1024, 128, 1 beam, windows 1 / 1 / 1, no wrap, max_recs 2^20, max_maps 1024, device 0. */
+void fmcw_merge_config_default(fmcw_merge_config* cfg);
+/* Validates every field before any device access (FMCW_EINVAL, the message names the field), then
+ * FMCW_ENODEV / FMCW_ENOMEM as fmcw_plots_create.  Allocates all scratch. */
+int fmcw_merge_create(const fmcw_merge_config* cfg, fmcw_merger** out);
+int fmcw_merge_destroy(fmcw_merger* m);   /* NULL is FMCW_OK */
+/* Device pointers only; stream-ordered, allocates nothing, never synchronises, uses no atomic and
+ * keeps no state between calls: every word a later launch reads is written by an earlier launch of
+ * the same call, so it can be captured into a hipGraph (after fmcw_plots_enqueue, say) and replayed.
+ * One stream at a time per merger.  rec_stride is 16 or 32; recs_dev and out_dev are 16-byte
+ * aligned; n_maps <= max_maps and a multiple of n_beams (FMCW_EINVAL otherwise, before any device
+ * access).  Examines n = min(n_recs_dev[0], rec_cap, max_recs) records (n is read on the device) and
+ * writes FMCW_MERGE_STATUS_WORDS words:
+ *   status_dev[0] merged plots found (may exceed out_cap: then the first out_cap are written and
+ *                 nothing is stored beyond them),
+ *   status_dev[1] n_recs_dev[0] - n, the records not examined,
+ *   status_dev[2] the examined records whose frame >= n_maps.  They form a suffix and are ignored:
+ *                 never a peak, never a neighbour, and no memory is indexed by them.
+ * With n = 0 it writes {0, n_recs_dev[0], 0} and touches nothing else. */
+int fmcw_merge_enqueue(fmcw_merger* m, const void* recs_dev, size_t rec_stride, size_t rec_cap,
+                       const uint32_t* n_recs_dev, size_t n_maps, fmcw_mplot* out_dev, size_t out_cap,
+                       uint32_t* status_dev, void* stream);
+/* Test hook: bounds the workgroups of the merger's tile kernels (index, find, emit), which stride
+ * over 1024-record tiles.  0 = the built-in bound (4096), else min(that bound, grid).  Merged plots
+ * never depend on it. */
+int fmcw_merge_set_grid_for_test(fmcw_merger* m, uint32_t grid);
 
 /* ---- Bearing estimation: rx snapshots and angle per detection ---------------------------
  * With n_rx > 1 the path integrates the channels non-coherently (FMCW_MAG_ABS) and the phase
