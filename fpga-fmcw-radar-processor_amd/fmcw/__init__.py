@@ -11,6 +11,7 @@ from .tracker import TwsTracker, TRACK_DTYPE  # noqa: F401
 from .tracker_dev import DeviceTwsTracker  # noqa: F401
 from .plots import PlotExtractor, PLOT_DTYPE  # noqa: F401
 from .merge import BeamMerger, MPLOT_DTYPE  # noqa: F401
+from .unfold import VelocityUnfolder, VPLOT_DTYPE, velocity_mps  # noqa: F401
 from .bearings import BearingEstimator, BEARING_DTYPE  # noqa: F401
 from .beams import BeamFormer, steering_weights  # noqa: F401
 from .adapt import AdaptiveWeights, steering_vectors, ADAPT_FALLBACK  # noqa: F401
@@ -18,5 +19,5 @@ from .cacfar import CaCfar  # noqa: F401
 from .cmap import ClutterMap  # noqa: F401
 from . import synth, formats  # noqa: F401
 
-__all__ = ["BeamMerger", "MPLOT_DTYPE", "AdaptiveWeights", "steering_vectors", "ADAPT_FALLBACK", "ClutterMap", "DeviceTwsTracker", "CaCfar", "BeamFormer", "steering_weights", "BearingEstimator", "BEARING_DTYPE", "PlotExtractor", "PLOT_DTYPE", "RadarCore", "RadarOutput", "DeviceBuffer", "DET_DTYPE", "FmcwError", "load",
+__all__ = ["VelocityUnfolder", "VPLOT_DTYPE", "velocity_mps", "BeamMerger", "MPLOT_DTYPE", "AdaptiveWeights", "steering_vectors", "ADAPT_FALLBACK", "ClutterMap", "DeviceTwsTracker", "CaCfar", "BeamFormer", "steering_weights", "BearingEstimator", "BEARING_DTYPE", "PlotExtractor", "PLOT_DTYPE", "RadarCore", "RadarOutput", "DeviceBuffer", "DET_DTYPE", "FmcwError", "load",
            "device_count", "magnitude", "TwsTracker", "TRACK_DTYPE", "synth", "formats", "pack_adc_words", "adc_words_to_cube"]

@@ -45,6 +45,7 @@ BEARING_STATUS_WORDS = 2  # FMCW_BEARING_STATUS_WORDS: n_out_dev = records proce
 CACFAR_CA, CACFAR_GO, CACFAR_SO = 0, 1, 2   # fmcw_cacfar_mode
 TWS_DEV_STATUS_WORDS = 2  # FMCW_TWS_DEV_STATUS_WORDS: status_dev = records not examined, out of range
 MERGE_STATUS_WORDS = 3   # FMCW_MERGE_STATUS_WORDS: status_dev = merged plots found, records not examined, out of range
+UNFOLD_STATUS_WORDS = 4  # FMCW_UNFOLD_STATUS_WORDS: status_dev = reports found, records not examined, out of range, tied
 BEARING_NO_ANGLE, BEARING_ONE_RX, BEARING_OUT_OF_RANGE = 1, 2, 4   # fmcw_bearing.flags bits
 
 STATUS_NAMES = {0: "FMCW_OK", -1: "FMCW_EINVAL", -2: "FMCW_ENOMEM", -3: "FMCW_EHIP",
@@ -96,6 +97,22 @@ class FmcwMergeConfig(C.Structure):
     _fields_ = [("n_range", C.c_uint32), ("n_doppler", C.c_uint32), ("n_beams", C.c_uint32),
                 ("win_beam", C.c_uint32), ("win_range", C.c_uint32), ("win_doppler", C.c_uint32),
                 ("beam_wrap", C.c_uint32), ("max_recs", C.c_uint32), ("max_maps", C.c_uint32),
+                ("device_id", C.c_int32)]
+
+
+class FmcwVplot(C.Structure):
+    _fields_ = [("frame", C.c_uint32), ("range", C.c_uint16), ("doppler", C.c_uint16),
+                ("mag", C.c_float), ("v_fine", C.c_int32), ("fold", C.c_int16), ("n_hits", C.c_uint8),
+                ("hit_mask", C.c_uint8), ("sum_mag", C.c_float), ("pos", C.c_uint16),
+                ("n_ties", C.c_uint16), ("src", C.c_uint32)]
+
+
+class FmcwUnfoldConfig(C.Structure):
+    _fields_ = [("n_range", C.c_uint32), ("n_doppler", C.c_uint32), ("n_prf", C.c_uint32),
+                ("prf_units", C.c_uint32 * 8), ("prf_phase", C.c_uint32), ("step", C.c_uint32),
+                ("zero_bin", C.c_uint32), ("v_max", C.c_uint32), ("out_unit", C.c_uint32),
+                ("tol_range", C.c_uint32), ("tol_doppler", C.c_uint32), ("m_of", C.c_uint32),
+                ("n_streams", C.c_uint32), ("max_recs", C.c_uint32), ("max_frames", C.c_uint32),
                 ("device_id", C.c_int32)]
 
 
@@ -197,6 +214,11 @@ SIGNATURES = {
     "fmcw_merge_destroy": (_I, [_VP]),
     "fmcw_merge_enqueue": (_I, [_VP, _VP, _SZ, _SZ, _VP, _SZ, _VP, _SZ, _VP, _VP]),
     "fmcw_merge_set_grid_for_test": (_I, [_VP, C.c_uint32]),
+    "fmcw_unfold_config_default": (None, [C.POINTER(FmcwUnfoldConfig)]),
+    "fmcw_unfold_create": (_I, [C.POINTER(FmcwUnfoldConfig), C.POINTER(_VP)]),
+    "fmcw_unfold_destroy": (_I, [_VP]),
+    "fmcw_unfold_enqueue": (_I, [_VP, _VP, _SZ, _SZ, _VP, _SZ, _VP, _SZ, _VP, _VP]),
+    "fmcw_unfold_set_grid_for_test": (_I, [_VP, C.c_uint32]),
     "fmcw_bearings_config_default": (None, [C.POINTER(FmcwBearingsConfig)]),
     "fmcw_bearings_create": (_I, [C.POINTER(FmcwBearingsConfig), C.POINTER(_VP)]),
     "fmcw_bearings_destroy": (_I, [_VP]),

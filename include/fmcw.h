@@ -103,6 +103,9 @@ extern "C" {
                                beamformer that never calls the new function behaves as before.
                                Still 8 with the beam merge (fmcw_merge_*, fmcw_mplot,
                                fmcw_merge_config): functions and types of its own, nothing
+                               existing changes.
+                               Still 8 with the velocity unfolder (fmcw_unfold_*, fmcw_vplot,
+                               fmcw_unfold_config): functions and types of its own, nothing
                                existing changes */
 
 typedef enum {
@@ -522,6 +525,114 @@ int fmcw_merge_enqueue(fmcw_merger* m, const void* recs_dev, size_t rec_stride, 
  * over 1024-record tiles.  0 = the built-in bound (4096), else min(that bound, grid).  Merged plots
  * never depend on it. */
 int fmcw_merge_set_grid_for_test(fmcw_merger* m, uint32_t grid);
+
+/* ---- Velocity unfolding: one report per target and dwell across a PRF stagger ------------
+ * A staggered radar changes its PRF from scan to scan, because one PRF folds a fast target's
+ * Doppler onto the wrong bin (and at a blind speed onto bin 0, where the canceller removes it).
+ * The unfolder turns every dwell of K staggered scans into one report per target with its
+ * unambiguous radial velocity, on a Doppler axis that is the same for every PRF.  A record list in,
+ * a record list out, on the device, from the lists alone; an object of its own, not part of
+ * fmcw_handle.
+ *
+ * Units.  PRF k (k = 0 .. n_prf - 1) is prf_units[k] * f0 = p_k f0 for a common f0.  The fine unit
+ * of frequency is f0 / n_doppler, so one Doppler bin of PRF k is p_k fine units.
+ * Input: a record list and its count word.  A record begins {uint32 frame; uint16 range; uint16
+ * doppler; float mag}; the stride is 16 (fmcw_det) or 32 (fmcw_plot, fmcw_mplot).  Records are
+ * strictly increasing in (frame, range, doppler).  Record frame m is scan s = m / n_streams of
+ * stream t = m % n_streams, as fmcw_tws_dev_enqueue reads it; streams never interact.  Scan s uses
+ * PRF index (s + prf_phase) % n_prf.  Dwell j covers scans j step .. j step + K - 1 (K = n_prf);
+ * there are n_dwells = (n_scans - K) / step + 1 of them, none if n_scans < K.
+ *
+ * A record P = (scan s, stream t, r, d, mag) belongs to every dwell j that contains s, at position
+ * i = s - j step, with PRF index k.  With Nc = n_doppler and all integers exact:
+ *   1. ds = (d - zero_bin) mod Nc, minus Nc if ds >= (Nc + 1) / 2;
+ *   2. the hypotheses are v_m = (ds + m Nc) p_k for every integer m with |v_m| <= v_max, ascending m;
+ *   3. at another position i' (scan s', PRF index k') v_m predicts the bin
+ *      d' = (floor((2 v_m + p_k') / (2 p_k')) + zero_bin) mod Nc;
+ *   4. position i' is a hit if stream t's scan s' holds a record (r + dr, (d' + dd) mod Nc) with
+ *      |dr| <= tol_range, 0 <= r + dr < n_range, |dd| <= tol_doppler; the hit's record is the one of
+ *      largest mag in that window, the first in list order among equals; P's own position is always a
+ *      hit, with P as its record;
+ *   5. the best hypothesis has the most hits, then the smaller |v|, then the smaller m; n_ties counts
+ *      the hypotheses that share the best hit count;
+ *   6. P reports in dwell j iff the best hypothesis has at least m_of hits and none of them at a
+ *      position before i: the earliest scan that sees the target owns the report.
+ * Reports come out in the order (dwell j, stream t, list order of P within that stream's scans of
+ * the dwell), so the output's .frame = j n_streams + t never decreases, as the device tracker
+ * requires; with one stream that is dwell, then list order.  NaN magnitudes are outside the
+ * specification.
+ *
+ * 32-bit arithmetic on the device: out_unit's limit gives v_max < 2^31, so every |v_m| fits an
+ * int32; floor((2 v + p) / (2 p)) is computed as floor(v / p) plus one if twice the remainder
+ * reaches p, which stays within int32; .doppler is formed from the uint32 v + v_max < 2^32 in the
+ * same way.  A record lies in at most ceil(K / step) dwells, and max_recs ceil(K / step) < 2^31
+ * bounds every (dwell, record) index. */
+typedef struct fmcw_vplot {   /* 32 bytes: fmcw_tws_dev_enqueue takes it at stride 32 */
+  uint32_t frame;            /* j n_streams + t: dwell j of stream t */
+  uint16_t range;            /* P's */
+  uint16_t doppler;          /* floor((2 (v + v_max) + out_unit) / (2 out_unit)): the unfolded axis */
+  float mag;                 /* P's, bit for bit */
+  int32_t v_fine;            /* v of the best hypothesis, in fine units (f0 / n_doppler) */
+  int16_t fold;              /* its m */
+  uint8_t n_hits;            /* positions of the dwell that hold the target, P's included */
+  uint8_t hit_mask;          /* bit i' set for a hit at position i' */
+  float sum_mag;             /* fp32 sum of the hit records' mag in ascending position */
+  uint16_t pos;              /* P's position i in the dwell */
+  uint16_t n_ties;           /* hypotheses with n_hits hits, the best included */
+  uint32_t src;              /* index of P in the input list (its plot centroid is there) */
+} fmcw_vplot;
+typedef struct fmcw_unfold_config {   /* 23 words, 92 bytes */
+  uint32_t n_range;          /* 1..65536 */
+  uint32_t n_doppler;        /* 2 tol_doppler + 1 .. 65536 */
+  uint32_t n_prf;            /* K, 2..8 */
+  uint32_t prf_units[8];     /* p_k, 1..4096, pairwise distinct over the first K; the rest is ignored */
+  uint32_t prf_phase;        /* 0..K-1 */
+  uint32_t step;             /* 1..K: scans from one dwell to the next */
+  uint32_t zero_bin;         /* 0..n_doppler-1: the bin of zero Doppler (0, or n_doppler / 2 for shifted bins) */
+  uint32_t v_max;            /* fine units, 0 .. 32 n_doppler min p_k */
+  uint32_t out_unit;         /* 1..65535 fine units per output Doppler bin, 2 v_max / out_unit + 1 <= 65535 */
+  uint32_t tol_range;        /* 0..4 */
+  uint32_t tol_doppler;      /* 0..4 */
+  uint32_t m_of;             /* 1..K: hits a report needs */
+  uint32_t n_streams;        /* 1..4096 */
+  uint32_t max_recs;         /* most records one call examines, >= 1, max_recs ceil(K / step) < 2^31;
+                                scratch per (dwell, record) pair, at most ceil(K / step) per record:
+                                4 B + 1 bit, and 8 B per 1024 of them */
+  uint32_t max_frames;       /* most frames (scans * n_streams) one call covers: >= n_streams, a multiple
+                                of it, max_frames K < 2^31; scratch: 4 (K + 1) B per frame */
+  int32_t device_id;         /* 0..63 */
+} fmcw_unfold_config;
+typedef struct fmcw_unfolder fmcw_unfolder;
+/* Status words of fmcw_unfold_enqueue (status_dev). */
+#define FMCW_UNFOLD_STATUS_WORDS 4
+/* Defaults: 1024 x 128, K 3 with units 8 / 9 / 10, phase 0, step 3, zero_bin 0, v_max 2 * 128 * 8,
+ * out_unit 8, tolerances 1 / 1, m_of 2, 1 stream, max_recs 2^20, max_frames 1024, device 0. */
+void fmcw_unfold_config_default(fmcw_unfold_config* cfg);
+/* Validates every field before any device access (FMCW_EINVAL, the message names the field), then
+ * FMCW_ENODEV / FMCW_ENOMEM as fmcw_plots_create.  Allocates all scratch. */
+int fmcw_unfold_create(const fmcw_unfold_config* cfg, fmcw_unfolder** out);
+int fmcw_unfold_destroy(fmcw_unfolder* u);   /* NULL is FMCW_OK */
+/* Device pointers only; stream-ordered, allocates nothing, never synchronises, uses no atomic and
+ * keeps no state between calls: every word a later launch reads is written by an earlier launch of
+ * the same call, so it can be captured into a hipGraph (after fmcw_plots_enqueue or
+ * fmcw_merge_enqueue, before fmcw_tws_dev_enqueue) and replayed.  One stream at a time per
+ * unfolder.  rec_stride is 16 or 32; recs_dev and out_dev are 16-byte aligned; n_scans * n_streams
+ * <= max_frames (FMCW_EINVAL otherwise, before any device access).  Examines n = min(n_recs_dev[0],
+ * rec_cap, max_recs) records (n is read on the device) and writes FMCW_UNFOLD_STATUS_WORDS words:
+ *   status_dev[0] reports found (may exceed out_cap: then the first out_cap are written and nothing
+ *                 is stored beyond them),
+ *   status_dev[1] n_recs_dev[0] - n, the records not examined,
+ *   status_dev[2] the examined records whose frame >= n_scans * n_streams.  They form a suffix and
+ *                 are ignored: never a hit, never a report, and no memory is indexed by them,
+ *   status_dev[3] reports found whose n_ties > 1.
+ * With n = 0 it writes {0, n_recs_dev[0], 0, 0} and touches nothing else. */
+int fmcw_unfold_enqueue(fmcw_unfolder* u, const void* recs_dev, size_t rec_stride, size_t rec_cap,
+                        const uint32_t* n_recs_dev, size_t n_scans, fmcw_vplot* out_dev, size_t out_cap,
+                        uint32_t* status_dev, void* stream);
+/* Test hook: bounds the workgroups of the unfolder's tile kernels (index, find, emit), which stride
+ * over 1024-item tiles.  0 = the built-in bound (4096), else min(that bound, grid).  Reports never
+ * depend on it. */
+int fmcw_unfold_set_grid_for_test(fmcw_unfolder* u, uint32_t grid);
 
 /* ---- Bearing estimation: rx snapshots and angle per detection ---------------------------
  * With n_rx > 1 the path integrates the channels non-coherently (FMCW_MAG_ABS) and the phase
