@@ -7,11 +7,9 @@
 // track per beam.  This is the azimuth centroiding of a surveillance plot extractor, kept in the shape
 // of the plotter (fmcw_plots.hip): a list in, a list out, device-resident, stream-ordered, no state.
 //
-// Four launches (merge_kernel.hpp): k_merge_index, k_merge_find, k_merge_scan, k_merge_emit.  No
+// Four launches (merge_kernel.hpp): k_frame_index, k_merge_find, k_merge_scan, k_merge_emit.  No
 // workgroup waits on another, no atomic and no counter that outlives a call.
 #include <hip/hip_runtime.h>
-
-#include <algorithm>
 
 #include "internal.hpp"
 #include "merge_kernel.hpp"
@@ -46,7 +44,6 @@ int validate(const fmcw_merge_config& c) {
 
 struct fmcw_merger {
   fmcw_merge_config cfg;
-  uint32_t max_tiles = 0;
   uint32_t grid = kMaxGrid;      // workgroups of index / find / emit at most (fmcw_merge_set_grid_for_test)
   uint64_t* masks = nullptr;     // kGroups per tile: 1 bit per record
   uint32_t* tile_cnt = nullptr;  // per tile: peak count, then its exclusive scan
@@ -77,13 +74,11 @@ int fmcw_merge_create(const fmcw_merge_config* cfg, fmcw_merger** out) {
   if ((rc = fmcw::open_device(cfg->device_id))) return rc;
   fmcw_merger* m = new fmcw_merger();
   m->cfg = *cfg;
-  m->max_tiles = (uint32_t)(((uint64_t)cfg->max_recs + kTile - 1) / kTile);
-  const size_t mask_bytes = (size_t)m->max_tiles * kGroups * sizeof(uint64_t), cnt_bytes = (size_t)m->max_tiles * 4;
+  const size_t max_tiles = fmcw::tiles_of(cfg->max_recs, MergeTiles::kTile);
+  const size_t mask_bytes = max_tiles * MergeTiles::kGroups * sizeof(uint64_t), cnt_bytes = max_tiles * 4;
   const size_t start_bytes = ((size_t)cfg->max_maps + 1) * 4;
-  if (hipMalloc(reinterpret_cast<void**>(&m->masks), mask_bytes) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&m->tile_cnt), cnt_bytes) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&m->start), start_bytes) != hipSuccess) {
-    (void)hipGetLastError();
+  if (!fmcw::alloc_scratch({fmcw::scratch(m->masks, mask_bytes), fmcw::scratch(m->tile_cnt, cnt_bytes),
+                            fmcw::scratch(m->start, start_bytes)})) {
     fmcw_merge_destroy(m);
     return fail(FMCW_ENOMEM, "hipMalloc(%zu + %zu + %zu) for the merger's masks, tile counts and map index failed",
                 mask_bytes, cnt_bytes, start_bytes);
@@ -95,9 +90,7 @@ int fmcw_merge_create(const fmcw_merge_config* cfg, fmcw_merger** out) {
 int fmcw_merge_destroy(fmcw_merger* m) {
   if (!m) return FMCW_OK;
   hipSetDevice(m->cfg.device_id);
-  if (m->masks) hipFree(m->masks);
-  if (m->tile_cnt) hipFree(m->tile_cnt);
-  if (m->start) hipFree(m->start);
+  fmcw::free_scratch({m->masks, m->tile_cnt, m->start});
   delete m;
   return FMCW_OK;
 }
@@ -112,39 +105,31 @@ int fmcw_merge_enqueue(fmcw_merger* m, const void* recs_dev, size_t rec_stride, 
                        const uint32_t* n_recs_dev, size_t n_maps, fmcw_mplot* out_dev, size_t out_cap,
                        uint32_t* status_dev, void* stream) {
   // what does not depend on the merger first, so that it can be checked without one
-  if (rec_stride != 16 && rec_stride != 32) return fail(FMCW_EINVAL, "rec_stride %zu (16 or 32)", rec_stride);
-  if (rec_cap && !recs_dev) return fail(FMCW_EINVAL, "null recs_dev with rec_cap %zu", rec_cap);
-  if (!n_recs_dev) return fail(FMCW_EINVAL, "null n_recs_dev");
-  if (out_cap && !out_dev) return fail(FMCW_EINVAL, "null out_dev with out_cap %zu", out_cap);
-  if (!status_dev) return fail(FMCW_EINVAL, "null status_dev");
-  if (int rc = fmcw::aligned(recs_dev, 16, "recs_dev")) return rc;
-  if (int rc = fmcw::aligned(out_dev, 16, "out_dev")) return rc;
+  if (int rc = fmcw::check_rec_list_args(recs_dev, rec_stride, rec_cap, n_recs_dev, out_dev, out_cap, status_dev)) return rc;
   if (!m) return fail(FMCW_EINVAL, "null merger");
   if (n_maps > m->cfg.max_maps) return fail(FMCW_EINVAL, "n_maps %zu above max_maps %u", n_maps, m->cfg.max_maps);
   if (n_maps % m->cfg.n_beams)
     return fail(FMCW_EINVAL, "n_maps %zu is not a multiple of n_beams %u", n_maps, m->cfg.n_beams);
   if (hipSetDevice(m->cfg.device_id) != hipSuccess) return fail(FMCW_EHIP, "hipSetDevice");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const uint32_t cap = (uint32_t)std::min<size_t>(rec_cap, m->cfg.max_recs);  // n = min(n_recs_dev[0], cap)
+  const fmcw::ListPlan lp = fmcw::plan_list(rec_cap, m->cfg.max_recs, 1, MergeTiles::kTile, m->grid);
   const uint32_t ocap = (uint32_t)std::min<size_t>(out_cap, 0x7fffffffu);      // n < 2^31 merged plots at most
-  const uint32_t tiles = (uint32_t)(((uint64_t)cap + kTile - 1) / kTile);       // <= max_tiles
-  const MergeList l = {static_cast<const uint8_t*>(recs_dev), (uint32_t)rec_stride, cap, n_recs_dev, m->start,
-                       (uint32_t)n_maps};
-  const MergeGeom g = {m->cfg.n_range, m->cfg.n_doppler, m->cfg.n_beams, m->cfg.win_beam,
-                       m->cfg.win_range, m->cfg.win_doppler, m->cfg.beam_wrap};
-  const dim3 grid(std::min(tiles, m->grid));
-  if (tiles) {
-    // cap + 1 items: one tile more than the records' when cap is a multiple of the tile
-    const dim3 gi(std::min(cap / kTile + 1, m->grid));
-    hipLaunchKernelGGL(k_merge_index, gi, dim3(kThreads), 0, s, l, m->start);
-    if (int rc = fmcw::check_launch("k_merge_index")) return rc;
-    hipLaunchKernelGGL(k_merge_find, grid, dim3(kThreads), 0, s, l, g, m->masks, m->tile_cnt);
+  const RecList l = {static_cast<const uint8_t*>(recs_dev), (uint32_t)rec_stride, lp.cap, n_recs_dev, m->start,
+                     (uint32_t)n_maps};
+  const WalkGeom g = {m->cfg.n_range, m->cfg.n_doppler, m->cfg.n_beams, m->cfg.win_beam,
+                      m->cfg.win_range, m->cfg.win_doppler, m->cfg.beam_wrap};
+  const dim3 grid(lp.grid), threads(MergeTiles::kThreads);
+  if (lp.tiles) {
+    hipLaunchKernelGGL((k_frame_index<MergeTiles::kThreads, MergeTiles::kPer, true>), dim3(lp.index_grid), threads, 0, s,
+                       l.recs, l.stride, l.cap, l.n_recs, l.n_groups, m->start);
+    if (int rc = fmcw::check_launch("k_frame_index")) return rc;
+    hipLaunchKernelGGL(k_merge_find, grid, threads, 0, s, l, g, m->masks, m->tile_cnt);
     if (int rc = fmcw::check_launch("k_merge_find")) return rc;
   }
   hipLaunchKernelGGL(k_merge_scan, dim3(1), dim3(kScanThreads), 0, s, l, m->tile_cnt, status_dev);
   if (int rc = fmcw::check_launch("k_merge_scan")) return rc;
-  if (tiles && ocap) {
-    hipLaunchKernelGGL(k_merge_emit, grid, dim3(kThreads), 0, s, l, g, m->masks, m->tile_cnt, out_dev, ocap);
+  if (lp.tiles && ocap) {
+    hipLaunchKernelGGL(k_merge_emit, grid, threads, 0, s, l, g, m->masks, m->tile_cnt, out_dev, ocap);
     if (int rc = fmcw::check_launch("k_merge_emit")) return rc;
   }
   return FMCW_OK;

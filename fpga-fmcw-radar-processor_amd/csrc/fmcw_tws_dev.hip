@@ -4,7 +4,7 @@
 // wave mapping are described in tws_dev_kernel.hpp.
 //
 // Two launches per call, nothing allocated, no synchronisation, no word that has to be cleared between
-// calls: k_tws_index writes every start word the tracker reads, and k_tws_track (the last kernel) also
+// calls: k_frame_index (rec_tiles.hpp) writes every start word the tracker reads, and k_tws_track (the last kernel) also
 // writes the two status words.  The track files live in the handle's state block and persist from call
 // to call; fmcw_tws_dev_reset puts them back to power-up in stream order.
 #include <hip/hip_runtime.h>
@@ -132,9 +132,9 @@ int fmcw_tws_dev_enqueue(fmcw_tws_dev* t, const void* recs_dev, size_t rec_strid
   const uint8_t* recs = static_cast<const uint8_t*>(recs_dev);
   const uint32_t tiles = cap / kIdxTile + 1;
   const uint32_t gi = std::min(tiles, fmcw::clamp_grid(t->grid, kIdxMaxGrid));
-  hipLaunchKernelGGL(k_tws_index, dim3(gi), dim3(kIdxThreads), 0, s, recs, (uint32_t)rec_stride, cap, n_recs_dev,
-                     n_groups, t->start);
-  if (int rc = fmcw::check_launch("k_tws_index")) return rc;
+  hipLaunchKernelGGL((fmcw_rec::k_frame_index<kIdxThreads, kIdxPer, false>), dim3(gi), dim3(kIdxThreads), 0, s, recs,
+                     (uint32_t)rec_stride, cap, n_recs_dev, n_groups, t->start);
+  if (int rc = fmcw::check_launch("k_frame_index")) return rc;
   const uint32_t wgs = (n_streams + kTrackWaves - 1) / kTrackWaves;   // one wave per stream
   const uint32_t gt = n_scans ? std::min(wgs, fmcw::clamp_grid(t->grid, kTrackMaxGrid)) : 1u;
   auto track = t->cfg.tws.rtl_compat ? k_tws_track<true> : k_tws_track<false>;

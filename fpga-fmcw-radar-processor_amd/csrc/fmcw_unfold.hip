@@ -7,7 +7,7 @@
 // the M-of-K coincidence unfolding of a medium-PRF radar, kept in the shape of the beam merger
 // (fmcw_merge.hip): a list in, a list out, device-resident, stream-ordered, no state.
 //
-// Five launches (unfold_kernel.hpp): k_unfold_index and k_unfold_dwells (the frame index and, from it,
+// Five launches (unfold_kernel.hpp): k_frame_index and k_unfold_dwells (the frame index and, from it,
 // the index of the (dwell, record) pairs), k_unfold_find, k_unfold_scan, k_unfold_emit.  No workgroup
 // waits on another, no atomic and no counter that outlives a call.
 #include <hip/hip_runtime.h>
@@ -24,6 +24,7 @@ static_assert(sizeof(fmcw_vplot) == 32 && sizeof(fmcw_unfold_config) == 92, "fmc
 namespace {
 
 using namespace fmcw_unfold;
+using fmcw_rec::k_frame_index;
 
 uint32_t dwells_per_record(const fmcw_unfold_config& c) { return (c.n_prf + c.step - 1) / c.step; }
 
@@ -66,7 +67,6 @@ int validate(const fmcw_unfold_config& c) {
 struct fmcw_unfolder {
   fmcw_unfold_config cfg;
   UnfoldGeom geom;
-  uint32_t max_tiles = 0;        // tiles of max_recs ceil(K / step) pairs
   uint32_t grid = kMaxGrid;      // workgroups of index / find / emit at most (fmcw_unfold_set_grid_for_test)
   uint64_t* masks = nullptr;     // kGroups per tile: 1 bit per pair
   uint32_t* tile_cnt = nullptr;  // per tile: report count, then its exclusive scan
@@ -111,17 +111,14 @@ int fmcw_unfold_create(const fmcw_unfold_config* cfg, fmcw_unfolder** out) {
   for (uint32_t k = 0; k < cfg->n_prf; ++k) units[k >> 2] |= (uint64_t)cfg->prf_units[k] << (16 * (k & 3));
   u->geom = UnfoldGeom{cfg->n_range, cfg->n_doppler, cfg->n_prf, cfg->prf_phase, cfg->step, cfg->zero_bin, cfg->v_max,
                        cfg->out_unit, cfg->tol_range, cfg->tol_doppler, cfg->m_of, cfg->n_streams, units[0], units[1]};
-  u->max_tiles = (uint32_t)(((uint64_t)cfg->max_recs * dwells_per_record(*cfg) + kTile - 1) / kTile);
-  const size_t mask_bytes = (size_t)u->max_tiles * kGroups * sizeof(uint64_t), cnt_bytes = (size_t)u->max_tiles * 4;
-  const size_t fold_bytes = (size_t)u->max_tiles * kTile * 4;
+  // tiles of max_recs ceil(K / step) pairs
+  const size_t max_tiles = fmcw::tiles_of((uint64_t)cfg->max_recs * dwells_per_record(*cfg), UnfoldTiles::kTile);
+  const size_t mask_bytes = max_tiles * UnfoldTiles::kGroups * sizeof(uint64_t), cnt_bytes = max_tiles * 4;
+  const size_t fold_bytes = max_tiles * UnfoldTiles::kTile * 4;
   const size_t start_bytes = ((size_t)cfg->max_frames + 1) * 4, vstart_bytes = ((size_t)cfg->max_frames * cfg->n_prf + 1) * 4;
-  if (hipMalloc(reinterpret_cast<void**>(&u->masks), mask_bytes) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&u->tile_cnt), cnt_bytes) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&u->tie_cnt), cnt_bytes) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&u->folds), fold_bytes) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&u->start), start_bytes) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&u->vstart), vstart_bytes) != hipSuccess) {
-    (void)hipGetLastError();
+  if (!fmcw::alloc_scratch({fmcw::scratch(u->masks, mask_bytes), fmcw::scratch(u->tile_cnt, cnt_bytes),
+                            fmcw::scratch(u->tie_cnt, cnt_bytes), fmcw::scratch(u->folds, fold_bytes),
+                            fmcw::scratch(u->start, start_bytes), fmcw::scratch(u->vstart, vstart_bytes)})) {
     fmcw_unfold_destroy(u);
     return fail(FMCW_ENOMEM, "hipMalloc(%zu + 2 x %zu + %zu + %zu + %zu) for the unfolder's masks, tile counts, folds and indices failed",
                 mask_bytes, cnt_bytes, fold_bytes, start_bytes, vstart_bytes);
@@ -133,8 +130,7 @@ int fmcw_unfold_create(const fmcw_unfold_config* cfg, fmcw_unfolder** out) {
 int fmcw_unfold_destroy(fmcw_unfolder* u) {
   if (!u) return FMCW_OK;
   hipSetDevice(u->cfg.device_id);
-  for (void* p : {(void*)u->masks, (void*)u->tile_cnt, (void*)u->tie_cnt, (void*)u->folds, (void*)u->start, (void*)u->vstart})
-    if (p) hipFree(p);
+  fmcw::free_scratch({u->masks, u->tile_cnt, u->tie_cnt, u->folds, u->start, u->vstart});
   delete u;
   return FMCW_OK;
 }
@@ -149,44 +145,37 @@ int fmcw_unfold_enqueue(fmcw_unfolder* u, const void* recs_dev, size_t rec_strid
                         const uint32_t* n_recs_dev, size_t n_scans, fmcw_vplot* out_dev, size_t out_cap,
                         uint32_t* status_dev, void* stream) {
   // what does not depend on the unfolder first, so that it can be checked without one
-  if (rec_stride != 16 && rec_stride != 32) return fail(FMCW_EINVAL, "rec_stride %zu (16 or 32)", rec_stride);
-  if (rec_cap && !recs_dev) return fail(FMCW_EINVAL, "null recs_dev with rec_cap %zu", rec_cap);
-  if (!n_recs_dev) return fail(FMCW_EINVAL, "null n_recs_dev");
-  if (out_cap && !out_dev) return fail(FMCW_EINVAL, "null out_dev with out_cap %zu", out_cap);
-  if (!status_dev) return fail(FMCW_EINVAL, "null status_dev");
-  if (int rc = fmcw::aligned(recs_dev, 16, "recs_dev")) return rc;
-  if (int rc = fmcw::aligned(out_dev, 16, "out_dev")) return rc;
+  if (int rc = fmcw::check_rec_list_args(recs_dev, rec_stride, rec_cap, n_recs_dev, out_dev, out_cap, status_dev)) return rc;
   if (!u) return fail(FMCW_EINVAL, "null unfolder");
   const fmcw_unfold_config& c = u->cfg;
   if (n_scans > c.max_frames / c.n_streams)
     return fail(FMCW_EINVAL, "n_scans %zu x n_streams %u above max_frames %u", n_scans, c.n_streams, c.max_frames);
   if (hipSetDevice(c.device_id) != hipSuccess) return fail(FMCW_EHIP, "hipSetDevice");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const uint32_t cap = (uint32_t)std::min<size_t>(rec_cap, c.max_recs);    // n = min(n_recs_dev[0], cap)
+  // cap x ceil(K / step) pairs, < 2^31 (validate)
+  const fmcw::ListPlan lp = fmcw::plan_list(rec_cap, c.max_recs, dwells_per_record(c), UnfoldTiles::kTile, u->grid);
   const uint32_t ocap = (uint32_t)std::min<size_t>(out_cap, 0x7fffffffu);   // fewer than 2^31 reports
-  const uint32_t v_cap = cap * dwells_per_record(c);                        // < 2^31 (validate)
-  const uint32_t tiles = (uint32_t)(((uint64_t)v_cap + kTile - 1) / kTile);  // <= max_tiles
   const uint32_t n_dwells = n_scans >= c.n_prf ? (uint32_t)((n_scans - c.n_prf) / c.step) + 1 : 0u;
-  const UnfoldList l = {static_cast<const uint8_t*>(recs_dev), (uint32_t)rec_stride, cap, n_recs_dev, u->start, u->vstart,
-                        (uint32_t)n_scans * c.n_streams, n_dwells * c.n_streams * c.n_prf, v_cap};   // n_q <= max_frames K
-  const dim3 grid(std::min(tiles, u->grid));
-  const bool pairs = tiles && l.n_q;
-  if (tiles) {
-    // cap + 1 items: one tile more than the records' when cap is a multiple of the tile
-    const dim3 gi(std::min(cap / kTile + 1, u->grid));
-    hipLaunchKernelGGL(k_unfold_index, gi, dim3(kThreads), 0, s, l, u->start);
-    if (int rc = fmcw::check_launch("k_unfold_index")) return rc;
+  const UnfoldList l = {{static_cast<const uint8_t*>(recs_dev), (uint32_t)rec_stride, lp.cap, n_recs_dev, u->start,
+                         (uint32_t)n_scans * c.n_streams},
+                        u->vstart, n_dwells * c.n_streams * c.n_prf, lp.cap * dwells_per_record(c)};   // n_q <= max_frames K
+  const dim3 grid(lp.grid), threads(UnfoldTiles::kThreads);
+  const bool pairs = lp.tiles && l.n_q;
+  if (lp.tiles) {
+    hipLaunchKernelGGL((k_frame_index<UnfoldTiles::kThreads, UnfoldTiles::kPer, true>), dim3(lp.index_grid), threads, 0, s,
+                       l.recs, l.stride, l.cap, l.n_recs, l.n_groups, u->start);
+    if (int rc = fmcw::check_launch("k_frame_index")) return rc;
   }
   if (pairs) {
     hipLaunchKernelGGL(k_unfold_dwells, dim3(1), dim3(kScanThreads), 0, s, l, u->geom, u->vstart);
     if (int rc = fmcw::check_launch("k_unfold_dwells")) return rc;
-    hipLaunchKernelGGL(k_unfold_find, grid, dim3(kThreads), 0, s, l, u->geom, u->masks, u->tile_cnt, u->tie_cnt, u->folds);
+    hipLaunchKernelGGL(k_unfold_find, grid, threads, 0, s, l, u->geom, u->masks, u->tile_cnt, u->tie_cnt, u->folds);
     if (int rc = fmcw::check_launch("k_unfold_find")) return rc;
   }
   hipLaunchKernelGGL(k_unfold_scan, dim3(1), dim3(kScanThreads), 0, s, l, u->tile_cnt, u->tie_cnt, status_dev);
   if (int rc = fmcw::check_launch("k_unfold_scan")) return rc;
   if (pairs && ocap) {
-    hipLaunchKernelGGL(k_unfold_emit, grid, dim3(kThreads), 0, s, l, u->geom, u->masks, u->tile_cnt, u->folds, out_dev, ocap);
+    hipLaunchKernelGGL(k_unfold_emit, grid, threads, 0, s, l, u->geom, u->masks, u->tile_cnt, u->folds, out_dev, ocap);
     if (int rc = fmcw::check_launch("k_unfold_emit")) return rc;
   }
   return FMCW_OK;

@@ -50,6 +50,31 @@ int check_map_and_dets(const float* map_dev, size_t n_frames, const fmcw_det* de
   return aligned(dets_dev, 16, "dets_dev");
 }
 
+int check_rec_list_args(const void* recs_dev, size_t rec_stride, size_t rec_cap, const uint32_t* n_recs_dev,
+                        const void* out_dev, size_t out_cap, const uint32_t* status_dev) {
+  if (rec_stride != 16 && rec_stride != 32) return fail(FMCW_EINVAL, "rec_stride %zu (16 or 32)", rec_stride);
+  if (rec_cap && !recs_dev) return fail(FMCW_EINVAL, "null recs_dev with rec_cap %zu", rec_cap);
+  if (!n_recs_dev) return fail(FMCW_EINVAL, "null n_recs_dev");
+  if (out_cap && !out_dev) return fail(FMCW_EINVAL, "null out_dev with out_cap %zu", out_cap);
+  if (!status_dev) return fail(FMCW_EINVAL, "null status_dev");
+  if (int rc = aligned(recs_dev, 16, "recs_dev")) return rc;
+  return aligned(out_dev, 16, "out_dev");
+}
+
+bool alloc_scratch(std::initializer_list<ScratchBuf> bufs) {
+  for (const ScratchBuf& b : bufs)
+    if (hipMalloc(b.ptr, b.bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      return false;
+    }
+  return true;
+}
+
+void free_scratch(std::initializer_list<void*> ptrs) {
+  for (void* p : ptrs)
+    if (p) hipFree(p);
+}
+
 int raise_lds_limit(std::initializer_list<const void*> fns, size_t bytes, const char* name) {
   for (const void* fn : fns)
     if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {

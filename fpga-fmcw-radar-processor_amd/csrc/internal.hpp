@@ -38,6 +38,41 @@ int aligned(const void* p, unsigned bytes, const char* name);
 // What the detectors' enqueue ask of their map and their list, in this order: map_dev present (with
 // n_frames) and 16-byte aligned, dets_dev present (with det_cap) and 16-byte aligned.
 int check_map_and_dets(const float* map_dev, size_t n_frames, const fmcw_det* dets_dev, size_t det_cap);
+// What the enqueue of a list-in / list-out object (merger, unfolder) asks of its arguments before it
+// looks at the object, in this order: rec_stride 16 or 32, recs_dev (with rec_cap), n_recs_dev, out_dev
+// (with out_cap) and status_dev present, recs_dev and out_dev 16-byte aligned.
+int check_rec_list_args(const void* recs_dev, size_t rec_stride, size_t rec_cap, const uint32_t* n_recs_dev,
+                        const void* out_dev, size_t out_cap, const uint32_t* status_dev);
+
+// An object's device scratch: alloc_scratch() fills every pointer of the list or returns false with the
+// pending HIP error cleared (the caller then destroys the object and reports FMCW_ENOMEM with its own
+// text); free_scratch() frees those that are set.
+struct ScratchBuf {
+  void** ptr;
+  size_t bytes;
+};
+template <class T>
+ScratchBuf scratch(T*& p, size_t bytes) { return {reinterpret_cast<void**>(&p), bytes}; }
+bool alloc_scratch(std::initializer_list<ScratchBuf> bufs);
+void free_scratch(std::initializer_list<void*> ptrs);
+
+// The sizes of one call on a record list, for kernels that stride over tiles of `tile` items:
+// cap = min(rec_cap, max_recs) records examined at most; tiles of its cap x items_per_rec items;
+// workgroups of the tile kernels; workgroups of the frame index, whose cap + 1 items are one tile more
+// than the records' when cap is a multiple of the tile.  `grid`: the object's bound (clamp_grid).
+inline uint32_t tiles_of(uint64_t items, uint32_t tile) { return (uint32_t)((items + tile - 1) / tile); }
+struct ListPlan {
+  uint32_t cap, tiles, grid, index_grid;
+};
+inline ListPlan plan_list(size_t rec_cap, uint32_t max_recs, uint32_t items_per_rec, uint32_t tile, uint32_t grid) {
+  ListPlan p;
+  p.cap = (uint32_t)std::min<size_t>(rec_cap, max_recs);   // n = min(n_recs_dev[0], cap)
+  p.tiles = tiles_of((uint64_t)p.cap * items_per_rec, tile);   // <= the tiles the scratch was sized for
+  p.grid = std::min(p.tiles, grid);
+  p.index_grid = std::min(p.cap / tile + 1, grid);
+  return p;
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize = bytes on each kernel of `fns` ("<name>: .. refused").
 // The attribute is per kernel, not per object: pass the largest any configuration needs, so that it
 // does not shrink when a second object is created.

@@ -4,12 +4,9 @@
 // wrap / resize_s / floor_shr8 over 64-bit integers in both modes, so there is no bound to argue: a
 // track that coasts for coast_max = 2^32 - 1 scans moves its position past 32 bits on the host too).
 //
-//   k_tws_index   start[g] = the first record whose frame is >= g, for g = 0 .. G (G = n_scans *
-//                 n_streams).  Persistent over tiles of kIdxTile = 1024 items; item i (0 .. n, one more
-//                 than the records) compares frame[i-1] and frame[i] (frame[-1] "before 0", frame[n]
-//                 "after the last") and writes start[g] = i for every g in (frame[i-1], min(frame[i], G)].
-//                 Empty frames, leading and trailing gaps get their empty ranges from the same store
-//                 loop.  Only the 4-byte frame word of a record is read.  Because the list is ordered,
+//   k_frame_index start[g] = the first record whose frame is >= g, for g = 0 .. G (G = n_scans *
+//                 n_streams): the shared index of rec_tiles.hpp over tiles of kIdxTile = 1024 items, here
+//                 also for an empty list (every start word is 0 then).  Because the list is ordered,
 //                 the records at or beyond frame G are the suffix from start[G]: the tracker kernel
 //                 reports n - start[G] as status word 1, so no counter has to be zeroed between calls.
 //   k_tws_track   one wave64 per workgroup and per stream (s = blockIdx.x; s += gridDim.x), serial over
@@ -39,13 +36,14 @@
 #include <cstdint>
 
 #include "../../include/fmcw.h"
+#include "rec_tiles.hpp"
 
 namespace fmcw_twsd {
 
 constexpr int kIdxThreads = 256;
 constexpr int kIdxPer = 4;
 constexpr uint32_t kIdxTile = kIdxThreads * kIdxPer;   // items per tile
-constexpr uint32_t kIdxMaxGrid = 1024;                  // workgroups of k_tws_index at most
+constexpr uint32_t kIdxMaxGrid = 1024;                  // workgroups of the index at most
 constexpr uint32_t kTrackMaxGrid = 4096;                // workgroups (waves) of k_tws_track at most
 constexpr uint32_t kMaxRecs = 0x7fffffffu;              // n + 1 items fit 32 bits
 
@@ -134,24 +132,6 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
   FMCW_TWS_DPP_MIN(0x143, 0xc);   // row_bcast:31 into rows 2 and 3
 #undef FMCW_TWS_DPP_MIN
   return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-
-__global__ void __launch_bounds__(kIdxThreads) k_tws_index(const uint8_t* __restrict__ recs, uint32_t stride,
-                                                           uint32_t cap, const uint32_t* __restrict__ n_recs,
-                                                           uint32_t n_groups, uint32_t* __restrict__ start) {
-  const uint32_t n = min(n_recs[0], cap);   // cap <= kMaxRecs
-  const uint32_t n_tiles = n / kIdxTile + 1;   // ceil((n + 1) / kIdxTile)
-  const int64_t G = (int64_t)n_groups;
-  for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-    for (int k = 0; k < kIdxPer; ++k) {
-      const uint32_t i = t * kIdxTile + (uint32_t)k * kIdxThreads + threadIdx.x;
-      if (i > n) continue;
-      const int64_t prev = i ? (int64_t) * reinterpret_cast<const uint32_t*>(recs + (size_t)(i - 1) * stride) : -1;
-      int64_t cur = G;
-      if (i < n) cur = min((int64_t) * reinterpret_cast<const uint32_t*>(recs + (size_t)i * stride), G);
-      for (int64_t g = prev + 1; g <= cur; ++g) start[g] = i;   // 0 <= g <= G: start holds G + 1 words at least
-    }
-  }
 }
 
 __global__ void __launch_bounds__(256) k_tws_reset(uint32_t* __restrict__ state, uint32_t n_streams) {

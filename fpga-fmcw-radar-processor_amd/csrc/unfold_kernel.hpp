@@ -8,9 +8,9 @@
 // is the virtual index of slot q's first pair.  Tiles, ballot masks and the tile scan run over
 // virtual indices, so output order needs no sort and a pair's rank is a popcount, as in the merger.
 //
-//   k_unfold_index   start[m] = the first record whose frame is >= m, for m = 0 .. n_frames (k_merge_index
-//                    restated: a plain __global__ cannot be shared between translation units).  The later
-//                    launches take n_use = min(start[n_frames], n) as the list's length.
+//   k_frame_index    start[m] = the first record whose frame is >= m, for m = 0 .. n_frames (rec_tiles.hpp,
+//                    over tiles of the unfolder's shape).  The later launches take
+//                    n_use = min(start[n_frames], n) as the list's length.
 //   k_unfold_dwells  one workgroup: vstart[q] = exclusive scan of the slots' segment lengths
 //                    (tile_offsets_scan), vstart[n_q] = their sum.
 //   k_unfold_find    one lane per pair: its slot by a search in vstart, then every hypothesis of the
@@ -28,66 +28,47 @@
 // counts and folds of the tiles below the virtual length) is written by an earlier launch of the same
 // call: nothing to zero between calls, no atomic.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
-#include "det_sink.hpp"
+#include "rec_tiles.hpp"
 #include "unfold_window.hpp"
 
 namespace fmcw_unfold {
 
-constexpr int kThreads = 1024;               // 16 waves: a lane's work is a chain of dependent searches, so a
-constexpr int kPer = 1;                      // tile's pairs run side by side (4 per lane in turn took 265 us, not 96, on a short list)
-constexpr uint32_t kTile = kThreads * kPer;  // pairs per tile
-constexpr int kGroups = kTile / 64;          // ballot masks per tile
+using fmcw_rec::RecList;
+using fmcw_rec::examined;
+
+// 16 waves: a lane's work is a chain of dependent searches, so a tile's pairs run side by side (4 per
+// lane in turn took 265 us, not 96, on a short list)
+using UnfoldTiles = fmcw_rec::Tiles<1024, 1>;
 constexpr uint32_t kMaxGrid = 4096;          // workgroups of index / find / emit (they stride over the tiles)
 constexpr int kScanThreads = 1024;
 
 // What one call reads its list through; by value to every kernel.
-struct UnfoldList {
-  const uint8_t* recs;
-  uint32_t stride, cap;        // cap = min(rec_cap, max_recs)
-  const uint32_t* n_recs;
-  const uint32_t* start;       // n_frames + 1 words
+struct UnfoldList : RecList {  // start: n_frames + 1 words, n_groups = n_frames = n_scans n_streams
   const uint32_t* vstart;      // n_q + 1 words
-  uint32_t n_frames, n_q;      // n_scans n_streams; n_dwells n_streams K
+  uint32_t n_q;                // n_dwells n_streams K
   uint32_t v_cap;              // cap ceil(K / step): what the per-pair scratch holds
 };
 
-__device__ __forceinline__ uint32_t examined(const UnfoldList& l) { return min(l.n_recs[0], l.cap); }
-// the records that take part: those below frame n_frames
+// The records that take part: those below frame n_frames.  Not rec_tiles.hpp's in_use() and scan_status(): the
+// unfolder always has an index, and their test for a list without one (a branch in every kernel's
+// prologue, the status words no longer one store in the one-workgroup scan) cost it 0.5 - 1 % per call.
 __device__ __forceinline__ uint32_t in_use(const UnfoldList& l) {
   const uint32_t n = examined(l);
-  return n ? min(l.start[l.n_frames], n) : 0u;
+  return n ? min(l.start[l.n_groups], n) : 0u;
 }
 // the (dwell, record) pairs; an ordered list never reaches v_cap
 __device__ __forceinline__ uint32_t virtual_len(const UnfoldList& l) {
-  return examined(l) ? min(l.vstart[l.n_q], l.v_cap) : 0u;
+  return l.n_q && examined(l) ? min(l.vstart[l.n_q], l.v_cap) : 0u;
 }
-__device__ __forceinline__ RecList rec_list(const UnfoldList& l) { return RecList{l.recs, l.stride, in_use(l), l.start}; }
-
-__global__ void __launch_bounds__(kThreads) k_unfold_index(UnfoldList l, uint32_t* __restrict__ start) {
-  const uint32_t n = examined(l);
-  if (!n) return;                               // nothing reads start[] then
-  const uint32_t n_tiles = n / kTile + 1;       // ceil((n + 1) / kTile)
-  const int64_t G = (int64_t)l.n_frames;
-  for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-    for (int k = 0; k < kPer; ++k) {
-      const uint32_t i = t * kTile + (uint32_t)k * kThreads + threadIdx.x;
-      if (i > n) continue;
-      const int64_t prev = i ? (int64_t) * reinterpret_cast<const uint32_t*>(l.recs + (size_t)(i - 1) * l.stride) : -1;
-      int64_t cur = G;
-      if (i < n) cur = min((int64_t) * reinterpret_cast<const uint32_t*>(l.recs + (size_t)i * l.stride), G);
-      for (int64_t m = prev + 1; m <= cur; ++m) start[m] = i;   // 0 <= m <= n_frames: start holds max_frames + 1 words
-    }
-  }
+// the records that take part, read in place
+__device__ __forceinline__ RecView rec_view(const UnfoldList& l) {
+  return RecView{l.recs, l.stride, in_use(l), 0, 0, nullptr, nullptr, l.start};
 }
 
 // One workgroup: the slots' segment lengths, scanned in place.  vstart holds max_frames K + 1 words.
 __global__ void __launch_bounds__(kScanThreads) k_unfold_dwells(UnfoldList l, UnfoldGeom g, uint32_t* __restrict__ vstart) {
   if (!examined(l)) return;                     // nothing reads vstart[] then
-  const RecList rl = rec_list(l);
+  const RecView rl = rec_view(l);
   for (uint32_t q = threadIdx.x; q < l.n_q; q += kScanThreads) {
     uint32_t lo, hi;
     rl.segment(slot_of(g, q).m, lo, hi);
@@ -100,7 +81,7 @@ __global__ void __launch_bounds__(kScanThreads) k_unfold_dwells(UnfoldList l, Un
 
 // The slot and the record of virtual index v < virtual_len; false where the index does not hold up
 // (an unordered list): such a pair is never a report and indexes nothing.
-__device__ __forceinline__ bool locate(const UnfoldList& l, const UnfoldGeom& g, const RecList& rl, uint32_t v, Slot& s,
+__device__ __forceinline__ bool locate(const UnfoldList& l, const UnfoldGeom& g, const RecView& rl, uint32_t v, Slot& s,
                                        uint32_t& idx) {
   uint32_t lo = 0, hi = l.n_q - 1;              // the last slot whose vstart is <= v
   while (lo < hi) {
@@ -115,18 +96,19 @@ __device__ __forceinline__ bool locate(const UnfoldList& l, const UnfoldGeom& g,
   return v >= l.vstart[lo] && idx < b && rl.word(idx)[0] == s.m;
 }
 
-__global__ void __launch_bounds__(kThreads) k_unfold_find(UnfoldList l, UnfoldGeom g, uint64_t* __restrict__ masks,
-                                                           uint32_t* __restrict__ tile_cnt, uint32_t* __restrict__ tie_cnt,
-                                                           uint32_t* __restrict__ folds) {
-  __shared__ uint32_t s_cnt[kGroups], s_tie[kGroups];
-  const RecList rl = rec_list(l);
-  const uint32_t nv = l.n_q ? virtual_len(l) : 0u;
-  const uint32_t n_tiles = (nv + kTile - 1) / kTile;
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+__global__ void __launch_bounds__(UnfoldTiles::kThreads) k_unfold_find(UnfoldList l, UnfoldGeom g,
+                                                                        uint64_t* __restrict__ masks,
+                                                                        uint32_t* __restrict__ tile_cnt,
+                                                                        uint32_t* __restrict__ tie_cnt,
+                                                                        uint32_t* __restrict__ folds) {
+  using T = UnfoldTiles;
+  __shared__ uint32_t s_cnt[T::kGroups], s_tie[T::kGroups];
+  const RecView rl = rec_view(l);
+  const uint32_t nv = virtual_len(l);
+  const uint32_t n_tiles = T::count(nv);
   for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-    const uint32_t base = t * kTile;
-    for (int k = 0; k < kPer; ++k) {
-      const uint32_t v = base + k * kThreads + tid;
+    for (int k = 0; k < T::kPer; ++k) {
+      const uint32_t v = t * T::kTile + k * T::kThreads + threadIdx.x;
       bool keep = false, tied = false;
       if (v < nv) {
         Slot s;
@@ -141,21 +123,12 @@ __global__ void __launch_bounds__(kThreads) k_unfold_find(UnfoldList l, UnfoldGe
         }
         folds[v] = packed;                      // v < v_cap
       }
-      const uint64_t mk = __ballot(keep), mt = __ballot(tied);
-      if (lane == 0) {
-        const int grp = k * (kThreads / 64) + (int)wave;
-        masks[(size_t)t * kGroups + grp] = mk;
-        s_cnt[grp] = (uint32_t)__popcll(mk);
-        s_tie[grp] = (uint32_t)__popcll(mt);
-      }
+      T::put(__ballot(keep), t, k, masks, s_cnt);
+      T::tally(__ballot(tied), k, s_tie);
     }
     __syncthreads();
-    if (tid == 0) {
-      uint32_t c = 0, e = 0;
-      for (int j = 0; j < kGroups; ++j) c += s_cnt[j], e += s_tie[j];
-      tile_cnt[t] = c;
-      tie_cnt[t] = e;
-    }
+    T::sum(s_cnt, &tile_cnt[t]);
+    T::sum(s_tie, &tie_cnt[t]);
     __syncthreads();   // before the next tile's lanes overwrite the group counts
   }
 }
@@ -166,8 +139,7 @@ __global__ void __launch_bounds__(kScanThreads) k_unfold_scan(UnfoldList l, uint
   const uint32_t found = l.n_recs[0];
   const uint32_t n = min(found, l.cap);
   const uint32_t use = in_use(l);
-  const uint32_t nv = l.n_q ? virtual_len(l) : 0u;
-  const int n_tiles = (int)((nv + kTile - 1) / kTile);   // < 2^21, a tile has at most kTile reports
+  const int n_tiles = (int)UnfoldTiles::count(virtual_len(l));   // < 2^21, a tile has at most kTile reports
   const uint32_t ties = fmcw::tile_offsets_scan<kScanThreads>(tie_cnt, tie_cnt, n_tiles);   // only the sum is used
   const uint32_t sum = fmcw::tile_offsets_scan<kScanThreads>(tile_cnt, tile_cnt, n_tiles);
   if (threadIdx.x == 0) {
@@ -178,30 +150,25 @@ __global__ void __launch_bounds__(kScanThreads) k_unfold_scan(UnfoldList l, uint
   }
 }
 
-__global__ void __launch_bounds__(kThreads) k_unfold_emit(UnfoldList l, UnfoldGeom g, const uint64_t* __restrict__ masks,
-                                                           const uint32_t* __restrict__ tile_off,
-                                                           const uint32_t* __restrict__ folds, fmcw_vplot* __restrict__ out,
-                                                           uint32_t out_cap) {
-  __shared__ uint64_t s_m[kGroups];
-  const RecList rl = rec_list(l);
-  const uint32_t nv = l.n_q ? virtual_len(l) : 0u;
-  const uint32_t n_tiles = (nv + kTile - 1) / kTile;
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+__global__ void __launch_bounds__(UnfoldTiles::kThreads) k_unfold_emit(UnfoldList l, UnfoldGeom g,
+                                                                        const uint64_t* __restrict__ masks,
+                                                                        const uint32_t* __restrict__ tile_off,
+                                                                        const uint32_t* __restrict__ folds,
+                                                                        fmcw_vplot* __restrict__ out, uint32_t out_cap) {
+  using T = UnfoldTiles;
+  __shared__ uint64_t s_m[T::kGroups];
+  const RecView rl = rec_view(l);
+  const uint32_t n_tiles = T::count(virtual_len(l));
   for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-    const uint32_t base = t * kTile;
     const uint32_t off = tile_off[t];
     if (off >= out_cap) break;  // offsets only grow with t: nothing left to write for this workgroup
     __syncthreads();
-    if (tid < kGroups) s_m[tid] = masks[(size_t)t * kGroups + tid];
+    T::load_masks(masks, t, s_m);
     __syncthreads();
-    for (int k = 0; k < kPer; ++k) {
-      const int grp = k * (kThreads / 64) + (int)wave;  // pairs base + 64 grp ..: output order
-      uint32_t rank = off;
-      for (int j = 0; j < grp; ++j) rank += (uint32_t)__popcll(s_m[j]);
-      const uint64_t mk = s_m[grp];
-      rank += (uint32_t)__popcll(mk & ((1ull << lane) - 1ull));
-      const uint32_t v = base + k * kThreads + tid;
-      if (!((mk >> lane) & 1ull) || rank >= out_cap) continue;
+    for (int k = 0; k < T::kPer; ++k) {
+      uint32_t rank;
+      if (!T::rank(s_m, k, off, rank) || rank >= out_cap) continue;
+      const uint32_t v = t * T::kTile + k * T::kThreads + threadIdx.x;
       Slot s;
       uint32_t idx;
       if (!locate(l, g, rl, v, s, idx)) continue;   // find kept it, so this holds

@@ -1,16 +1,18 @@
 // unfold_window.hpp -- what one lane of the velocity unfolder (fmcw_unfold.hip) does for one record of
-// one dwell: the list view, the (dwell, stream, position) numbering, the hit search in another scan's
-// segment and the walk over the hypotheses.  Host and device code (plain C++, no LDS or cross-lane
-// operation, no array a lane indexes at run time), so that it can also be exercised on the CPU.
+// one dwell: the (dwell, stream, position) numbering, the hit search in another scan's segment and the
+// walk over the hypotheses, over the list view and the column runs of rec_window.hpp (nothing staged:
+// the view reads in place).  Host and device code (plain C++, no LDS or cross-lane operation), so that
+// it can also be exercised on the CPU.
 //
 // Integers: see include/fmcw.h -- |v| <= v_max < 2^31 and |v / p| <= 32 n_doppler + 1, so int32 holds
 // every intermediate; floor((2 v + p) / (2 p)) is floor(v / p) plus one if twice the remainder reaches p.
 #pragma once
-#include "plots_window.hpp"
+#include "rec_window.hpp"
 
 namespace fmcw_unfold {
 
-using fmcw_plots::umin;
+using fmcw_rec::RecView;
+using fmcw_rec::umin;
 
 constexpr uint32_t kNone = 0xffffffffu;
 
@@ -33,26 +35,6 @@ FMCW_HD int floordiv(int a, int b) {   // b > 0
   return q;
 }
 
-// The list as a lane sees it.  n counts the records that take part (those of a frame below n_scans
-// n_streams); start[m] is the first record of frame m or later, for m = 0 .. n_scans n_streams.
-struct RecList {
-  const uint8_t* recs;
-  uint32_t stride, n;
-  const uint32_t* start;
-  FMCW_HD const uint32_t* word(uint32_t i) const { return reinterpret_cast<const uint32_t*>(recs + (size_t)i * stride); }
-  // (range, doppler) as one ascending key; the frame is fixed inside a segment
-  FMCW_HD uint32_t key(uint32_t i) const {
-    const uint32_t rd = word(i)[1];   // range | doppler << 16
-    return (rd << 16) | (rd >> 16);
-  }
-  FMCW_HD float mag(uint32_t i) const { return reinterpret_cast<const float*>(word(i))[2]; }
-  // frame m's records [lo, hi): the index is trusted only as far as the list reaches
-  FMCW_HD void segment(uint32_t m, uint32_t& lo, uint32_t& hi) const {
-    hi = umin(start[m + 1], n);
-    lo = umin(start[m], hi);
-  }
-};
-
 // One (dwell, stream, position) triple q = (j n_streams + t) K + i and its frame m = (j step + i) n_streams + t.
 struct Slot {
   uint32_t j, t, i, m;
@@ -71,33 +53,27 @@ FMCW_HD Slot slot_of(const UnfoldGeom& g, uint32_t q) {
 // the segment [lo, hi) of one frame; the first in list order among equals; kNone if there is none.
 // Rows ascend and the (at most two) column runs of a row ascend, so the records are met in list
 // order and every lower bound lies at or after the one before it.
-FMCW_HD uint32_t window_hit(const RecList& l, const UnfoldGeom& g, uint32_t lo, const uint32_t hi, uint32_t r, uint32_t d) {
+FMCW_HD uint32_t window_hit(const RecView& l, const UnfoldGeom& g, uint32_t lo, const uint32_t hi, uint32_t r, uint32_t d) {
   if (lo >= hi) return kNone;
-  const int nd = (int)g.n_doppler, td = (int)g.tol_doppler, tr = (int)g.tol_range;
-  const int c_lo = (int)d - td, c_hi = (int)d + td;
-  int a0 = c_lo, b0 = c_hi, a1 = 0, b1 = -1;   // run [a1, b1] is empty unless the window wraps
-  if (c_lo < 0) {
-    a0 = 0, b0 = c_hi, a1 = c_lo + nd, b1 = nd - 1;
-  } else if (c_hi >= nd) {
-    a0 = 0, b0 = c_hi - nd, a1 = c_lo, b1 = nd - 1;
-  }
+  const int tr = (int)g.tol_range;
+  const fmcw_rec::ColumnRuns c = fmcw_rec::column_runs(d, g.tol_doppler, g.n_doppler);
   uint32_t best = kNone;
   float best_mag = 0.f;
   for (int dr = -tr; dr <= tr; ++dr) {
     const int rr = (int)r + dr;
     if (rr < 0 || rr >= (int)g.n_range) continue;
     for (int run = 0; run < 2; ++run) {
-      const int a = run ? a1 : a0, b = run ? b1 : b0;
+      const int a = c.a(run), b = c.b(run);
       if (b < a) continue;
       const uint32_t ka = ((uint32_t)rr << 16) | (uint32_t)a, kb = ((uint32_t)rr << 16) | (uint32_t)b;
       uint32_t top = hi;
       while (lo < top) {
         const uint32_t mid = (lo + top) >> 1;
-        if (l.key(mid) < ka) lo = mid + 1;
+        if (l.cell_key(mid) < ka) lo = mid + 1;
         else top = mid;
       }
       for (; lo < hi; ++lo) {
-        if (l.key(lo) > kb) break;
+        if (l.cell_key(lo) > kb) break;
         const float mq = l.mag(lo);
         if (best == kNone || mq > best_mag) best = lo, best_mag = mq;
       }
@@ -132,7 +108,7 @@ FMCW_HD uint32_t predicted_bin(const UnfoldGeom& g, int v, uint32_t p) {
 // Calls fn(position, record) for every hit of hypothesis v of record idx = (slot s, range r), in
 // ascending position; the record's own position is a hit with the record itself.
 template <class F>
-FMCW_HD void visit_hits(const RecList& l, const UnfoldGeom& g, const Slot& s, uint32_t idx, uint32_t r, int v, F&& fn) {
+FMCW_HD void visit_hits(const RecView& l, const UnfoldGeom& g, const Slot& s, uint32_t idx, uint32_t r, int v, F&& fn) {
   for (uint32_t i2 = 0; i2 < g.n_prf; ++i2) {
     if (i2 == s.i) {
       fn(i2, idx);
@@ -154,7 +130,7 @@ struct Verdict {
 };
 
 // Every hypothesis of record idx = (slot s, r, d): the best one, and whether the record reports.
-FMCW_HD Verdict judge(const RecList& l, const UnfoldGeom& g, const Slot& s, uint32_t idx, uint32_t r, uint32_t d) {
+FMCW_HD Verdict judge(const RecView& l, const UnfoldGeom& g, const Slot& s, uint32_t idx, uint32_t r, uint32_t d) {
   const uint32_t p = scan_unit(g, s.j * g.step + s.i);
   int ds, m_lo, m_hi;
   hypothesis_range(g, d, p, ds, m_lo, m_hi);
@@ -178,7 +154,7 @@ FMCW_HD Verdict judge(const RecList& l, const UnfoldGeom& g, const Slot& s, uint
 }
 
 // The report of record idx for its best hypothesis (fold, n_ties from judge()).
-FMCW_HD fmcw_vplot report(const RecList& l, const UnfoldGeom& g, const Slot& s, uint32_t idx, int fold, uint32_t n_ties) {
+FMCW_HD fmcw_vplot report(const RecView& l, const UnfoldGeom& g, const Slot& s, uint32_t idx, int fold, uint32_t n_ties) {
   const uint32_t rd = l.word(idx)[1], r = rd & 0xffffu, d = rd >> 16;
   const uint32_t p = scan_unit(g, s.j * g.step + s.i);
   int ds, m_lo, m_hi;

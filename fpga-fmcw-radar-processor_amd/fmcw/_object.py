@@ -1,5 +1,6 @@
 """What the wrappers of the objects beside RadarCore share (private): the handle's life cycle, the pointer
-argument of their enqueue calls, the staging of a host array and the detectors' run-twice loop."""
+argument of their enqueue calls, the staging of a host array and the run-twice loops of the detectors
+and of the list-in / list-out objects."""
 from __future__ import annotations
 
 import ctypes as C
@@ -101,3 +102,38 @@ def detect_maps(det, maps, det_cap, changed: str, before_rerun=None) -> np.ndarr
     finally:
         for b in own:
             b.free()
+
+
+def run_list(obj, recs: np.ndarray, count_words: int, status_words: int, out_dtype, cap: int, enqueue, changed: str):
+    """The synchronous call of a list-in / list-out object `obj` (device): uploads the contiguous host
+    records and their count word (the first of count_words uint32) and runs enqueue(recs_dev, n,
+    count_dev, out_dev, cap, status_dev), once more with the reported count when cap was short.  Returns
+    (host out_dtype records, the status_words status words).  `changed`: the RuntimeError text should
+    the count differ between the two runs."""
+    n = len(recs)
+    dr = DeviceBuffer(max(n, 1) * recs.dtype.itemsize, obj.device)
+    dn = DeviceBuffer(4 * count_words, obj.device)
+    ds = DeviceBuffer(4 * status_words, obj.device)
+    try:
+        if n:
+            dr.upload(recs)
+        count = np.zeros(count_words, np.uint32)
+        count[0] = n
+        dn.upload(count)
+        for _ in range(2):
+            do = DeviceBuffer(max(cap, 1) * out_dtype.itemsize, obj.device)
+            try:
+                enqueue(dr, n, dn, do, cap, ds)
+                # fmcw_memcpy is synchronous on the default stream the call ran on
+                status = ds.download(np.uint32, (status_words,))
+                found = int(status[0])
+                if found <= cap:
+                    return do.download(out_dtype, (found,)), status
+            finally:
+                do.free()
+            cap = found
+        raise RuntimeError(changed)
+    finally:
+        dr.free()
+        dn.free()
+        ds.free()

@@ -18,8 +18,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from ._object import DeviceObject, ptr
-from .radar_core import DeviceBuffer
+from ._object import DeviceObject, ptr, run_list
 
 MPLOT_DTYPE = np.dtype([("frame", "<u4"), ("range", "<u2"), ("doppler", "<u2"), ("mag", "<f4"),
                         ("beam", "<u2"), ("n_merged", "<u2"), ("sum_mag", "<f4"),
@@ -63,29 +62,9 @@ class BeamMerger(DeviceObject):
         if n > self.cfg.max_recs:
             raise ValueError(f"{n} records exceed this merger's max_recs {self.cfg.max_recs}")
         cap = max(n // 4, 64) if out_cap is None else out_cap
-        dr = DeviceBuffer(max(n, 1) * stride, self.device)
-        dn = DeviceBuffer(4, self.device)
-        ds = DeviceBuffer(4 * L.MERGE_STATUS_WORDS, self.device)
-        try:
-            if n:
-                dr.upload(r)
-            dn.upload(np.array([n], np.uint32))
-            for _ in range(2):
-                do = DeviceBuffer(max(cap, 1) * MPLOT_DTYPE.itemsize, self.device)
-                try:
-                    self.enqueue(dr, stride, n, dn, n_maps, do, cap, ds)
-                    # fmcw_memcpy is synchronous on the default stream the call ran on
-                    found = int(ds.download(np.uint32, (L.MERGE_STATUS_WORDS,))[0])
-                    if found <= cap:
-                        return do.download(MPLOT_DTYPE, (found,))
-                finally:
-                    do.free()
-                cap = found
-            raise RuntimeError("merged-plot count changed between two runs on the same list")
-        finally:
-            dr.free()
-            dn.free()
-            ds.free()
+        return run_list(self, r, 1, L.MERGE_STATUS_WORDS, MPLOT_DTYPE, cap,
+                        lambda dr, n, dn, do, cap, ds: self.enqueue(dr, stride, n, dn, n_maps, do, cap, ds),
+                        "merged-plot count changed between two runs on the same list")[0]
 
     def beam_position(self, mplots: np.ndarray) -> np.ndarray:
         """beam + d_beam in beams (fp64); with beam_wrap taken modulo n_beams."""

@@ -16,8 +16,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from ._object import DeviceObject, ptr
-from .radar_core import DET_DTYPE, DeviceBuffer
+from ._object import DeviceObject, ptr, run_list
+from .radar_core import DET_DTYPE
 
 PLOT_DTYPE = np.dtype([("frame", "<u4"), ("range", "<u2"), ("doppler", "<u2"), ("mag", "<f4"),
                        ("threshold", "<f4"), ("n_cells", "<u4"), ("sum_mag", "<f4"),
@@ -51,29 +51,8 @@ class PlotExtractor(DeviceObject):
         if n > self.cfg.max_dets:
             raise ValueError(f"{n} detections exceed this extractor's max_dets {self.cfg.max_dets}")
         cap = max(n // 4, 64) if plot_cap is None else plot_cap
-        dd = DeviceBuffer(max(n, 1) * DET_DTYPE.itemsize, self.device)
-        dn = DeviceBuffer(4 * L.STATUS_WORDS, self.device)
-        ds = DeviceBuffer(4 * L.PLOT_STATUS_WORDS, self.device)
-        try:
-            if n:
-                dd.upload(d)
-            dn.upload(np.array([n, 0, 0, 0], np.uint32))
-            for _ in range(2):
-                dp = DeviceBuffer(max(cap, 1) * PLOT_DTYPE.itemsize, self.device)
-                try:
-                    self.enqueue(dd, n, dn, dp, cap, ds)
-                    # fmcw_memcpy is synchronous on the default stream the call ran on
-                    found = int(ds.download(np.uint32, (L.PLOT_STATUS_WORDS,))[0])
-                    if found <= cap:
-                        return dp.download(PLOT_DTYPE, (found,))
-                finally:
-                    dp.free()
-                cap = found
-            raise RuntimeError("plot count changed between two runs on the same list")
-        finally:
-            dd.free()
-            dn.free()
-            ds.free()
+        return run_list(self, d, L.STATUS_WORDS, L.PLOT_STATUS_WORDS, PLOT_DTYPE, cap, self.enqueue,
+                        "plot count changed between two runs on the same list")[0]
 
     def set_grid_for_test(self, grid: int) -> None:
         """fmcw_plots_set_grid_for_test: at most `grid` workgroups for the two tile kernels (0: the

@@ -22,8 +22,7 @@ from math import gcd
 import numpy as np
 
 from . import _lib as L
-from ._object import DeviceObject, ptr
-from .radar_core import DeviceBuffer
+from ._object import DeviceObject, ptr, run_list
 
 VPLOT_DTYPE = np.dtype([("frame", "<u4"), ("range", "<u2"), ("doppler", "<u2"), ("mag", "<f4"),
                         ("v_fine", "<i4"), ("fold", "<i2"), ("n_hits", "u1"), ("hit_mask", "u1"),
@@ -104,30 +103,10 @@ class VelocityUnfolder(DeviceObject):
         if n > self.cfg.max_recs:
             raise ValueError(f"{n} records exceed this unfolder's max_recs {self.cfg.max_recs}")
         cap = max(n // 4, 64) if out_cap is None else out_cap
-        dr = DeviceBuffer(max(n, 1) * stride, self.device)
-        dn = DeviceBuffer(4, self.device)
-        ds = DeviceBuffer(4 * L.UNFOLD_STATUS_WORDS, self.device)
-        try:
-            if n:
-                dr.upload(r)
-            dn.upload(np.array([n], np.uint32))
-            for _ in range(2):
-                do = DeviceBuffer(max(cap, 1) * VPLOT_DTYPE.itemsize, self.device)
-                try:
-                    self.enqueue(dr, stride, n, dn, n_scans, do, cap, ds)
-                    # fmcw_memcpy is synchronous on the default stream the call ran on
-                    self.status = ds.download(np.uint32, (L.UNFOLD_STATUS_WORDS,))
-                    found = int(self.status[0])
-                    if found <= cap:
-                        return do.download(VPLOT_DTYPE, (found,))
-                finally:
-                    do.free()
-                cap = found
-            raise RuntimeError("report count changed between two runs on the same list")
-        finally:
-            dr.free()
-            dn.free()
-            ds.free()
+        out, self.status = run_list(self, r, 1, L.UNFOLD_STATUS_WORDS, VPLOT_DTYPE, cap,
+                                    lambda dr, n, dn, do, cap, ds: self.enqueue(dr, stride, n, dn, n_scans, do, cap, ds),
+                                    "report count changed between two runs on the same list")
+        return out
 
     def n_dwells(self, n_scans: int) -> int:
         k, step = self.cfg.n_prf, self.cfg.step

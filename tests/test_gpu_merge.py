@@ -22,7 +22,8 @@ from bearings_ref import assert_bearings_match, bearings_ref
 from merge_ref import HAND, assert_mplots_match, hand_records, merge_ref
 from plots_ref import assert_plots_match, plots_ref
 from test_gpu_r05 import _Hip
-from test_merge_host import random_list
+from test_merge_host import random_list, tile_edge_list
+from tile_edge import TILE_EDGE_SIZES
 
 pytestmark = pytest.mark.gpu
 
@@ -246,6 +247,23 @@ def test_empty_maps_in_the_middle_of_a_scan(gpu):
     for wrap in (False, True):
         check(recs, 32, 16, 5, (2, 1, 1), wrap, n_maps=15)
     check(recs[recs["frame"] >= 4], 32, 16, 5, (1, 1, 1), True, n_maps=15)    # a leading gap of four maps
+
+
+@pytest.mark.parametrize("n", TILE_EDGE_SIZES)
+def test_index_at_its_tile_edge(gpu, n):
+    """Lists of exactly 1023, 1024, 1025 and 2048 records (max_recs = n) that end in map 3 of 6: the words
+    of the empty maps 4 and 5 and start[n_maps] come from item i == n of the frame index, which at 1024
+    and 2048 is alone in a tile of its own.  The built-in grid and one workgroup."""
+    recs = tile_edge_list(n)
+    want, beyond = merge_ref(recs, 32, 32, 3, (1, 1, 1), False, 6)
+    assert beyond == 0 and len(want) > 0
+    with BeamMerger(32, 32, 3, win=(1, 1, 1), max_recs=n, max_maps=6) as mg:
+        for grid in (0, 1):
+            mg.set_grid_for_test(grid)
+            st, got, rest = run(mg, recs, 6)
+            assert list(st) == [len(want), 0, 0], (grid, st)
+            assert_mplots_match(got, want, (1, 1, 1))
+            assert np.all(rest == SENTINEL), grid
 
 
 def test_n_maps_checked_before_the_launch(gpu):

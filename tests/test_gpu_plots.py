@@ -14,7 +14,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, PKG
-from fmcw import RadarCore, DeviceBuffer, DET_DTYPE, PLOT_DTYPE, PlotExtractor, TwsTracker, formats, synth
+from fmcw import (RadarCore, BeamMerger, DeviceBuffer, DET_DTYPE, PLOT_DTYPE, PlotExtractor, TwsTracker, formats,
+                  synth)
 from plots_ref import plots_ref, assert_plots_match
 from test_gpu_r05 import _Hip
 
@@ -127,6 +128,28 @@ def test_larger_lists(gpu, density):
     dets = random_list(12, 2, 256, 128, density)
     check(dets, 256, 128, (1, 1))
     check(dets, 256, 128, (4, 4))
+
+
+@pytest.mark.parametrize("nf,nr,nd,density,win,grids", [(3, 16, 9, 0.5, (1, 1), (0,)), (3, 16, 9, 0.5, (4, 4), (0,)),
+                                                         (2, 64, 32, 1.0, (4, 4), (0, 1))])
+def test_equals_the_merger_on_one_beam(gpu, nf, nr, nd, density, win, grids):
+    """The plot extractor and the beam merger with one beam and win_beam 0 run the same walk, so on the
+    same ordered list their records agree bit for bit.  16 x 9: n_doppler = 2 * 4 + 1, the window wraps
+    on both sides at every cell.  64 x 32 x 2 at density 1: 4096 records, 4 tiles with halos on both
+    sides, under the built-in grid and under one workgroup."""
+    dets = random_list(71, nf, nr, nd, density)
+    assert density < 1.0 or len(dets) == 4096
+    with PlotExtractor(nr, nd, win=win, max_dets=len(dets)) as px, \
+            BeamMerger(nr, nd, 1, win=(0, *win), max_recs=len(dets), max_maps=nf) as mg:
+        for grid in grids:
+            px.set_grid_for_test(grid)
+            mg.set_grid_for_test(grid)
+            p, m = px.extract(dets), mg.merge(dets, nf)
+            assert len(p) == len(m) > 0
+            for name in ("frame", "range", "doppler", "mag", "sum_mag", "d_range", "d_doppler"):
+                assert p[name].tobytes() == m[name].tobytes(), (grid, name)
+            assert np.array_equal(p["n_cells"], m["n_merged"])
+            assert not m["d_beam"].any() and not m["beam"].any()
 
 
 def test_empty_list(gpu):

@@ -6,7 +6,7 @@ Everything is integer arithmetic, so every comparison is equality: each fmcw_tra
 n_active of every (scan, stream), both status words, and the sentinel bytes of every track slot beyond
 n_out.  No tolerance anywhere.
 
-k_tws_index works on tiles of 1024 items (kIdxTile, csrc/tws_dev_kernel.hpp): item i compares records
+The frame index (k_frame_index, csrc/rec_tiles.hpp) works on tiles of 1024 items (kIdxTile): item i compares records
 i - 1 and i, so a frame boundary "at records 1023 / 1024" is the first item of the second tile.
 """
 import functools

@@ -16,7 +16,8 @@ import tws_dev_ref as TR
 from fmcw import DET_DTYPE, PLOT_DTYPE, TRACK_DTYPE, VPLOT_DTYPE, DeviceBuffer, DeviceTwsTracker, PlotExtractor, VelocityUnfolder
 from plots_ref import assert_plots_match, plots_ref
 from test_gpu_r05 import _Hip
-from test_unfold_host import FIGHTER_FACT, fighter_fact, scenario_cfg
+from test_unfold_host import FIGHTER_FACT, TILE_EDGE_CFG, fighter_fact, scenario_cfg, tile_edge_list
+from tile_edge import TILE_EDGE_SIZES
 from unfold_ref import Cfg, assert_vplots_equal, n_dwells, random_list, unfold_ref
 
 pytestmark = pytest.mark.gpu
@@ -181,6 +182,17 @@ def test_frames_beyond_n_scans_and_too_few_scans(gpu, n_scans):
             assert list(st) == [len(want), 0, beyond, tied]
             assert_vplots_equal(got, want)
             assert np.all(rest == SENTINEL)
+
+
+@pytest.mark.parametrize("n", TILE_EDGE_SIZES)
+def test_index_at_its_tile_edge(gpu, n):
+    """Lists of exactly 1023, 1024, 1025 and 2048 records (max_recs = n) that end in frame 3 of 6: the words
+    of the empty frames 4 and 5 and start[n_frames] come from item i == n of the frame index, which at
+    1024 and 2048 is alone in a tile of its own.  One workgroup and the built-in grid."""
+    recs = tile_edge_list(n)
+    got, want = check(recs, 6, TILE_EDGE_CFG, grids=(0, 1))
+    assert len(want) > 0
+    assert unfold_ref(recs, 6, TILE_EDGE_CFG)[1] == 0   # check() compared status word 2 with this
 
 
 def test_n_scans_checked_before_the_launch(gpu):

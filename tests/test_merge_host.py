@@ -16,6 +16,7 @@ from fmcw import merge as M
 from beams_ref import beams_ref
 from merge_ref import HAND, hand_records, merge_ref
 from plots_ref import plots_ref
+from tile_edge import TILE_EDGE_SIZES, thin_to
 
 NEW_SYMBOLS = ("fmcw_merge_config_default", "fmcw_merge_create", "fmcw_merge_destroy", "fmcw_merge_enqueue",
                "fmcw_merge_set_grid_for_test")
@@ -154,6 +155,20 @@ def random_list(seed, n_maps, nr, nd, density, dtype=DET_DTYPE, levels=5):
     a["frame"], a["range"], a["doppler"] = f, r, d
     a["mag"] = rng.integers(1, levels + 1, len(f)).astype(np.float32)
     return a
+
+
+def tile_edge_list(n):
+    """Exactly n records of 32 x 32 maps whose last record is in frame 3: merged as 2 scans x 3 beams,
+    maps 4 and 5 are empty."""
+    recs = thin_to(random_list(40, 4, 32, 32, 0.7), n, n)
+    assert len(recs) == n and recs["frame"][-1] == 3
+    return recs
+
+
+@pytest.mark.parametrize("n", TILE_EDGE_SIZES)
+def test_tile_edge_lists_have_merged_plots(n):
+    want, beyond = merge_ref(tile_edge_list(n), 32, 32, 3, (1, 1, 1), False, 6)
+    assert beyond == 0 and len(want) > 0
 
 
 @pytest.mark.parametrize("win", [(1, 1), (0, 3), (4, 4), (2, 1)])

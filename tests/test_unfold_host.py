@@ -18,8 +18,9 @@ import pytest
 import scenario_ref as S
 from fmcw import DET_DTYPE, MPLOT_DTYPE, PLOT_DTYPE, VPLOT_DTYPE, VelocityUnfolder, synth, velocity_mps
 from fmcw import _lib as L
-from unfold_ref import (Cfg, VPLOT_REF_DTYPE, hypotheses, n_dwells, out_doppler, predicted_bin, records, signed_bin,
-                        unfold_ref)
+from tile_edge import TILE_EDGE_SIZES, thin_to
+from unfold_ref import (Cfg, VPLOT_REF_DTYPE, hypotheses, n_dwells, out_doppler, predicted_bin, random_list, records,
+                        signed_bin, unfold_ref)
 
 NEW_SYMBOLS = ("fmcw_unfold_config_default", "fmcw_unfold_create", "fmcw_unfold_destroy", "fmcw_unfold_enqueue",
                "fmcw_unfold_set_grid_for_test")
@@ -174,6 +175,23 @@ def test_streams_never_interact_and_order():
 
 
 # ---- layout and validation ---------------------------------------------------------------------
+TILE_EDGE_CFG = Cfg(n_range=64, n_doppler=32, v_max=3 * 32 * 8, step=3)   # K = 3, one stream
+
+
+def tile_edge_list(n):
+    """Exactly n records of 64 x 32 frames whose last record is in frame 3: unfolded as 6 scans (two
+    dwells), frames 4 and 5 are empty."""
+    recs = thin_to(random_list(41, 4, 64, 32, n + n // 4 + 64, DET_DTYPE, cfg=TILE_EDGE_CFG, targets=20), n, n)
+    assert len(recs) == n and recs["frame"][-1] == 3
+    return recs
+
+
+@pytest.mark.parametrize("n", TILE_EDGE_SIZES)
+def test_tile_edge_lists_have_reports(n):
+    want, beyond, _ = unfold_ref(tile_edge_list(n), 6, TILE_EDGE_CFG)
+    assert beyond == 0 and len(want) > 0
+
+
 def default_cfg(lib):
     cfg = L.FmcwUnfoldConfig()
     lib.fmcw_unfold_config_default(C.byref(cfg))
