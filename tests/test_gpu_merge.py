@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import fmcw_oracle as O
+import reclist_cases as RC
 import tws_dev_ref as TR
 from fmcw import (DET_DTYPE, MPLOT_DTYPE, PLOT_DTYPE, BeamFormer, BeamMerger, BearingEstimator, DeviceBuffer,
                   DeviceTwsTracker, PlotExtractor, RadarCore, steering_weights, synth)
@@ -264,6 +265,19 @@ def test_index_at_its_tile_edge(gpu, n):
             assert list(st) == [len(want), 0, 0], (grid, st)
             assert_mplots_match(got, want, (1, 1, 1))
             assert np.all(rest == SENTINEL), grid
+
+
+@pytest.mark.parametrize("wrap", [False, True])
+@pytest.mark.parametrize("dtype", [DET_DTYPE, PLOT_DTYPE], ids=["stride16", "stride32"])
+def test_corner_list_at_the_limits(gpu, dtype, wrap):
+    """n_range = n_doppler = 65536, records at the four corners and their neighbours across the Doppler wrap in
+    2 scans x 9 beams (and one map beyond them), windows (4, 4, 4) (reclist_cases.py; the list layer ran the same
+    lists on the CPU under sanitizers, test_reclist_replay.py).  max_recs is the list's length; one workgroup
+    and the built-in grid."""
+    m = RC.MERGE_CORNER
+    recs = RC.corner_list(m["n_maps"] + 1, dtype, seed=dtype.itemsize)
+    got, want = check(recs, RC.LIMIT, RC.LIMIT, m["n_beams"], m["win"], wrap, n_maps=m["n_maps"], grids=(1, 0))
+    assert len(want) > 0 and want["n_merged"].max() > 8
 
 
 def test_n_maps_checked_before_the_launch(gpu):

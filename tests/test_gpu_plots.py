@@ -13,6 +13,7 @@ import sys
 import numpy as np
 import pytest
 
+import reclist_cases as RC
 from conftest import GOLDEN, PKG
 from fmcw import (RadarCore, BeamMerger, DeviceBuffer, DET_DTYPE, PLOT_DTYPE, PlotExtractor, TwsTracker, formats,
                   synth)
@@ -150,6 +151,25 @@ def test_equals_the_merger_on_one_beam(gpu, nf, nr, nd, density, win, grids):
                 assert p[name].tobytes() == m[name].tobytes(), (grid, name)
             assert np.array_equal(p["n_cells"], m["n_merged"])
             assert not m["d_beam"].any() and not m["beam"].any()
+
+
+def test_corner_list_at_the_limits(gpu):
+    """n_range = n_doppler = 65536, records at the four corners and their neighbours across the Doppler wrap,
+    window (4, 4) (reclist_cases.py; the list layer ran the same list on the CPU under sanitizers,
+    test_reclist_replay.py).  max_dets is the list's length; one workgroup and the built-in grid, the same bytes."""
+    dets = RC.corner_list(3, DET_DTYPE)
+    want = plots_ref(dets, RC.LIMIT, RC.LIMIT, *RC.PLOTS_CORNER_WIN)
+    assert 0 < len(want) < len(dets) and want["n_cells"].max() > 4
+    first = None
+    with PlotExtractor(RC.LIMIT, RC.LIMIT, win=RC.PLOTS_CORNER_WIN, max_dets=len(dets)) as px:
+        for grid in (1, 0):
+            px.set_grid_for_test(grid)
+            st, got, rest = run(px, dets)
+            assert list(st) == [len(want), 0], (grid, st)
+            assert_plots_match(got, want)
+            assert np.all(rest == SENTINEL), grid
+            first = first or (got.tobytes(), rest.tobytes())
+            assert (got.tobytes(), rest.tobytes()) == first, grid
 
 
 def test_empty_list(gpu):

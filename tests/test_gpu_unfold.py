@@ -11,6 +11,7 @@ import itertools
 import numpy as np
 import pytest
 
+import reclist_cases as RC
 import scenario_ref as S
 import tws_dev_ref as TR
 from fmcw import DET_DTYPE, PLOT_DTYPE, TRACK_DTYPE, VPLOT_DTYPE, DeviceBuffer, DeviceTwsTracker, PlotExtractor, VelocityUnfolder
@@ -25,7 +26,7 @@ pytestmark = pytest.mark.gpu
 SENTINEL = 0xA5
 GUARD = 0xA5A5A5A5
 NR, NC, SCANS = 64, 32, 9
-UNITS = {2: (8, 9), 3: (8, 9, 10), 4: (7, 8, 9, 11)}
+UNITS = {2: (8, 9), 3: (8, 9, 10), 4: (7, 8, 9, 11), 5: (7, 8, 9, 11, 13), 8: (7, 8, 9, 11, 13, 15, 16, 17)}
 
 
 def unfolder(cfg: Cfg, max_recs, max_frames=None):
@@ -34,12 +35,12 @@ def unfolder(cfg: Cfg, max_recs, max_frames=None):
                             max_recs=max(max_recs, 1), max_frames=max_frames)
 
 
-def run(uf, recs, n_scans, out_cap=None, rec_cap=None, n_word=None):
+def run(uf, recs, n_scans, out_cap=None, rec_cap=None, n_word=None, K=4):
     """One fmcw_unfold_enqueue on a host list: (status words, reports written, the sentinel-filled
     output buffer's bytes after them).  The status words sit between guard words."""
     n, stride = len(recs), recs.dtype.itemsize
     rec_cap = n if rec_cap is None else rec_cap
-    out_cap = max(4 * n, 1) if out_cap is None else out_cap   # a record reports in at most K <= 4 dwells
+    out_cap = max(K * n, 1) if out_cap is None else out_cap   # a record reports in at most K dwells
     dr = DeviceBuffer(max(n, 1) * stride)
     if n:
         dr.upload(np.ascontiguousarray(recs))
@@ -68,7 +69,7 @@ def check(recs, n_scans, cfg, grids=(0,), max_recs=None, **kw):
     with unfolder(cfg, len(recs) if max_recs is None else max_recs) as uf:
         for grid in grids:
             uf.set_grid_for_test(grid)
-            st, got, rest = run(uf, recs, n_scans, **kw)
+            st, got, rest = run(uf, recs, n_scans, K=max(cfg.n_prf, 4), **kw)
             assert list(st) == [len(want), 0, beyond, tied], (grid, st, len(want), beyond, tied)
             assert_vplots_equal(got, want)
             assert np.all(rest == SENTINEL), grid
@@ -96,6 +97,44 @@ def test_random_lists(gpu, K, step, m_of):
         _, want = check(recs, SCANS, cfg)
         reports += len(want)
     assert reports > 0
+
+
+@pytest.mark.parametrize("K,step,m_of", sorted({(K, step, m_of) for K in (5, 8) for step in (1, K) for m_of in (1, K - 1, K)}))
+def test_random_lists_five_and_eight_prfs(gpu, K, step, m_of):
+    """K = 5 and 8 (the second word of PRF units, positions 4..7 of hit_mask): 64 x 32, 2 K + 1 scans, 200-300
+    records with movers, both strides, 1 and 2 streams; zero_bin, the tolerances and v_max take their two values
+    in turn.  Some report has a hit at a position >= 4, and some has all K."""
+    p = UNITS[K]
+    high = full = 0
+    for k, (dtype, ns) in enumerate(itertools.product((DET_DTYPE, PLOT_DTYPE), (1, 2))):
+        j = k + step + m_of
+        tol = (0, 2)[j % 2]
+        cfg = Cfg(n_range=NR, n_doppler=NC, prf_units=p, prf_phase=j % K, step=step, zero_bin=(0, NC // 2)[j // 2 % 2],
+                  v_max=(3 * NC * min(p), 0)[(j + k // 2) % 2 if k % 2 else 0], out_unit=min(p), tol_range=tol, tol_doppler=tol,
+                  m_of=m_of, n_streams=ns)
+        n_scans = 2 * K + 1
+        recs = random_list(2000 * K + k, n_scans * ns + 1, NR, NC, 200, dtype, cfg=cfg, targets=3)
+        assert 200 <= len(recs) <= 300, len(recs)
+        _, want = check(recs, n_scans, cfg, grids=(0, 1) if k == 0 else (0,))
+        high += int((want["hit_mask"] >> 4).astype(bool).sum())
+        full += int((want["n_hits"] == K).sum())
+    assert high > 0 and full > 0, (high, full)
+
+
+def test_v_max_limit_65_hypotheses(gpu):
+    """K = 3 at the admitted v_max limit 32 Nc p_min, 32 x 32 x 8 scans: 65 hypotheses per record."""
+    cfg, recs = RC.unfold_v_max_limit_case()
+    _, want = check(recs, 8, cfg, grids=(1, 0))
+    assert len(want) > 0 and want["n_ties"].max() > 1 and np.abs(want["fold"]).max() >= 16
+
+
+@pytest.mark.parametrize("dtype", [DET_DTYPE, PLOT_DTYPE], ids=["stride16", "stride32"])
+def test_corner_list_at_the_limits(gpu, dtype):
+    """n_range = n_doppler = 65536, records at the four corners and their neighbours across the Doppler wrap,
+    PRF units 4096 / 4095 / 4093, tolerances of 4 and a v_max within 2^17 of 2^31 (reclist_cases.py; the list
+    layer ran the same list on the CPU under sanitizers, test_reclist_replay.py).  max_recs is the list's length."""
+    _, want = check(RC.unfold_corner_list(dtype), RC.UNFOLD_CORNER_SCANS, RC.UNFOLD_CORNER_CFG, grids=(1, 0))
+    assert (want["n_hits"] == 3).sum() >= 4 and np.abs(want["v_fine"].astype(np.int64)).max() > 2 ** 31 - 2 ** 17
 
 
 @functools.lru_cache(maxsize=None)
