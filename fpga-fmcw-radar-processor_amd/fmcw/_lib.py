@@ -46,6 +46,8 @@ CACFAR_CA, CACFAR_GO, CACFAR_SO = 0, 1, 2   # fmcw_cacfar_mode
 TWS_DEV_STATUS_WORDS = 2  # FMCW_TWS_DEV_STATUS_WORDS: status_dev = records not examined, out of range
 MERGE_STATUS_WORDS = 3   # FMCW_MERGE_STATUS_WORDS: status_dev = merged plots found, records not examined, out of range
 UNFOLD_STATUS_WORDS = 4  # FMCW_UNFOLD_STATUS_WORDS: status_dev = reports found, records not examined, out of range, tied
+EXCISE_ZERO, EXCISE_INTERP = 0, 1   # fmcw_excise_mode
+EXCISE_STATUS_WORDS = 4  # FMCW_EXCISE_STATUS_WORDS: status_dev = samples repaired, lines repaired, samples flagged, lines over half
 BEARING_NO_ANGLE, BEARING_ONE_RX, BEARING_OUT_OF_RANGE = 1, 2, 4   # fmcw_bearing.flags bits
 
 STATUS_NAMES = {0: "FMCW_OK", -1: "FMCW_EINVAL", -2: "FMCW_ENOMEM", -3: "FMCW_EHIP",
@@ -148,6 +150,13 @@ class FmcwCaCfarConfig(C.Structure):
                 ("device_id", C.c_int32), ("reserved", C.c_uint32 * 2)]
 
 
+class FmcwExciseConfig(C.Structure):
+    _fields_ = [("n_range", C.c_uint32), ("n_doppler", C.c_uint32), ("n_rx", C.c_uint32),
+                ("in_dtype", C.c_int32), ("mode", C.c_int32), ("guard", C.c_uint32),
+                ("rank_pct", C.c_uint32), ("alpha", C.c_float), ("max_frames", C.c_uint32),
+                ("device_id", C.c_int32), ("reserved", C.c_uint32 * 2)]
+
+
 class FmcwCmapConfig(C.Structure):
     _fields_ = [("n_range", C.c_uint32), ("n_doppler", C.c_uint32), ("n_streams", C.c_uint32),
                 ("gain", C.c_float), ("alpha", C.c_float), ("floor", C.c_float), ("clip", C.c_float),
@@ -240,6 +249,11 @@ SIGNATURES = {
     "fmcw_cacfar_destroy": (_I, [_VP]),
     "fmcw_cacfar_enqueue": (_I, [_VP, _VP, _SZ, _VP, _SZ, _VP, _VP]),
     "fmcw_cacfar_set_grid_for_test": (_I, [_VP, C.c_uint32]),
+    "fmcw_excise_config_default": (None, [C.POINTER(FmcwExciseConfig)]),
+    "fmcw_excise_create": (_I, [C.POINTER(FmcwExciseConfig), C.POINTER(_VP)]),
+    "fmcw_excise_destroy": (_I, [_VP]),
+    "fmcw_excise_enqueue": (_I, [_VP, _VP, _SZ, _VP, _VP, _VP, _VP, _VP]),
+    "fmcw_excise_set_grid_for_test": (_I, [_VP, C.c_uint32]),
     "fmcw_cmap_config_default": (None, [C.POINTER(FmcwCmapConfig)]),
     "fmcw_cmap_create": (_I, [C.POINTER(FmcwCmapConfig), C.POINTER(_VP)]),
     "fmcw_cmap_destroy": (_I, [_VP]),

@@ -16,6 +16,10 @@ Outputs in --out-dir (names the visualizer searches, model/visualize_radar_targe
   --doppler-centred shifts Doppler bins by N/2 (fftshift) in both files
   --cfar ca|go|so [--ca-alpha 4] detects with the cell-averaging family (fmcw.cacfar: CA, greatest-of,
                  smallest-of; the 2-D window 4/1/4/2) on the map of the path run without a CFAR
+  --excise zero|interp [--excise-alpha 16 --excise-guard 4] repairs interference bursts in the ADC cube
+                 before anything else runs (fmcw.excise: per chirp, samples whose power exceeds alpha x the
+                 chirp's median power, widened by the guard, are zeroed or interpolated) and prints the
+                 four status words
   ADR_tracks.txt (with --tracks): the track-while-scan log, one scan per frame
                  ("TRK id R= D= Q=" / "SCAN_END ACTIVE=n", tb_radar_core.vhd:163-180);
                  --tracker gpu runs the device tracker (fmcw.tracker_dev) and writes the same file;
@@ -45,6 +49,7 @@ from . import formats, synth
 from .adapt import AdaptiveWeights, steering_vectors
 from .beams import BeamFormer, steering_weights
 from .cacfar import CaCfar
+from .excise import InterferenceExciser
 from .bearings import BearingEstimator
 from .plots import PlotExtractor
 from .radar_core import DET_DTYPE, DeviceBuffer, RadarCore, adc_words_to_cube
@@ -110,6 +115,12 @@ def build_parser():
     ap.add_argument("--adaptive", type=float, default=None, metavar="LOADING",
                     help="with --beams: adaptive (MVDR) weights for the same look directions, trained on the "
                          "call's frames, diagonal loading LOADING (finite, >= 0) of the mean channel power")
+    ap.add_argument("--excise", default=None, choices=["zero", "interp"],
+                    help="repair interference bursts in the ADC cube first: zero them, or interpolate across them")
+    ap.add_argument("--excise-alpha", type=float, default=16.0, metavar="ALPHA",
+                    help="with --excise: flag samples whose power exceeds ALPHA x the chirp's median (finite, >= 1)")
+    ap.add_argument("--excise-guard", type=int, default=4, metavar="SAMPLES",
+                    help="with --excise: samples repaired on each side of a flagged one (0..32)")
     return ap
 
 
@@ -180,9 +191,19 @@ def main(argv=None):
         ap.error("--beams needs a CFAR (os1d or os2d) to run on the beams' maps")
     if not (math.isfinite(a.ca_alpha) and a.ca_alpha > 0):
         ap.error("--ca-alpha must be finite and positive")
+    if not (math.isfinite(a.excise_alpha) and a.excise_alpha >= 1):
+        ap.error("--excise-alpha must be finite and >= 1")
+    if not 0 <= a.excise_guard <= 32:
+        ap.error("--excise-guard must be in 0..32")
     ca = a.cfar in CA_MODES
     cube, dt = load_cube(a.input, a.n_range, a.n_doppler)
     nf, nrx = cube.shape[0], cube.shape[1]
+    if a.excise:   # the interference exciser on the cube, in front of everything else
+        with InterferenceExciser(a.n_range, a.n_doppler, n_rx=nrx, in_dtype=dt, mode=a.excise, guard=a.excise_guard,
+                                 alpha=a.excise_alpha, max_frames=nf, device=a.device) as ex:
+            cube, _, _, st = ex.repair(np.ascontiguousarray(cube))
+        print(f"excise {a.excise}: {st[0]} samples repaired in {st[1]} chirps ({st[2]} flagged before the guard, "
+              f"{st[3]} chirps more than half repaired)")
     if a.beams and nrx < 2:
         ap.error(f"--beams needs multi-rx input ({a.input} has one channel)")
     if a.adaptive is not None and nrx > 16:

@@ -63,6 +63,45 @@ def frames(n_frames: int, ns: int, nc: int, n_rx: int = 1, recipe: str = "two_ta
     return np.stack([frame(ns, nc, n_rx, recipe, seed + f, dtype, rx_phase) for f in range(n_frames)])
 
 
+def interference_bursts(cube: np.ndarray, every: int, length: int, amplitude: float, seed: int, sweep: float = 0.002):
+    """Mutual interference: another FMCW radar's chirp crossing ours.  In every `every`-th chirp (chirps
+    0, every, 2 every, ...) of each frame and rx of `cube` -- complex [..., chirp, sample], or float16 /
+    int16 [..., chirp, sample, 2] -- adds the burst amplitude exp(2 pi i (phi + f n + sweep n^2 / 2)),
+    n = 0 .. length - 1, a linear FM crossing of `sweep` cycles per sample^2, at a random first sample in
+    0 .. Ns - length, start frequency f in [-0.5, 0.5) cycles per sample and phase phi.  RNG: numpy
+    PCG64 from `seed`; the first samples of all hit chirps, then their frequencies, then their phases,
+    each in the cube's own order.  int16 cubes are rounded and saturated.
+
+    Returns (a new cube of the same shape and dtype, true_mask bool [..., chirp, sample])."""
+    cube = np.asarray(cube)
+    pairs = not np.iscomplexobj(cube)
+    z = (cube[..., 0] + 1j * cube[..., 1]) if pairs else cube.astype(np.complex128)
+    z = np.array(z, np.complex128)
+    nc, ns = z.shape[-2:]
+    if not (1 <= length <= ns and every >= 1):
+        raise ValueError(f"every {every}, length {length}: need every >= 1 and 1 <= length <= {ns}")
+    rng = np.random.Generator(np.random.PCG64(seed))
+    hit = np.arange(0, nc, every)
+    shape = z.shape[:-2] + (len(hit),)
+    first = rng.integers(0, ns - length + 1, shape)
+    f0 = rng.uniform(-0.5, 0.5, shape)
+    phi = rng.uniform(0.0, 1.0, shape)
+    n = np.arange(length, dtype=np.float64)
+    burst = amplitude * np.exp(2j * np.pi * (phi[..., None] + f0[..., None] * n + 0.5 * sweep * n * n))
+    at = first[..., None] + np.arange(length)                     # [..., hit, length] sample indices
+    true_mask = np.zeros(z.shape, bool)
+    lead = np.indices(shape)
+    idx = tuple(i[..., None] for i in lead[:-1]) + (hit[lead[-1]][..., None], at)
+    z[idx] += burst
+    true_mask[idx] = True
+    if not pairs:
+        return z.astype(cube.dtype), true_mask
+    iq = np.stack([z.real, z.imag], axis=-1)
+    if cube.dtype == np.int16:
+        iq = np.clip(np.rint(iq), -32768, 32767)
+    return iq.astype(cube.dtype), true_mask
+
+
 def ieee_uniform(seed1: int, seed2: int, n: int):
     """IEEE 1076.2 MATH_REAL.UNIFORM (L'Ecuyer's combined multiplicative LCG, the RNG of every
     reference testbench): n draws from (seed1, seed2); returns (draws float64, seed1, seed2)."""

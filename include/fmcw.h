@@ -106,7 +106,10 @@ extern "C" {
                                existing changes.
                                Still 8 with the velocity unfolder (fmcw_unfold_*, fmcw_vplot,
                                fmcw_unfold_config): functions and types of its own, nothing
-                               existing changes */
+                               existing changes.
+                               Still 8 with the interference exciser (fmcw_excise_*,
+                               fmcw_excise_config): functions and types of its own, in front of
+                               fmcw_enqueue; nothing existing changes */
 
 typedef enum {
   FMCW_OK = 0,
@@ -1172,6 +1175,83 @@ int fmcw_tws_dev_enqueue(fmcw_tws_dev* t, const void* recs_dev, size_t rec_strid
  * short list drives one workgroup of the index kernel through several 1024-record tiles and one wave
  * of the tracker through several streams.  Results never depend on it. */
 int fmcw_tws_dev_set_grid_for_test(fmcw_tws_dev* t, uint32_t grid);
+
+/* ---- Interference excision: blank or interpolate bursts in the ADC cube before the range FFT ----
+ * Another FMCW radar's chirp crossing ours leaves a short burst in some chirps, 30-60 dB above the
+ * noise.  A burst in fast time is white in range: it raises the whole range profile of the chirps it
+ * hits and, after the Doppler FFT, the whole map, and every CFAR downstream adapts to the raised floor.
+ * The exciser finds the burst per chirp against a robust level of the chirp's own power and repairs it
+ * before the window and the range FFT: its output is a cube fmcw_enqueue / fmcw_range_ct take as it is.
+ *
+ * Cube.  [frame][rx][chirp][sample] in any fmcw_in_dtype, as fmcw_enqueue reads it; the repaired cube
+ * has the same layout and dtype.  A line is one chirp of one rx of one frame: Ns = n_range complex
+ * samples.  Lines are independent.  The specification is exact: every step below is one individually
+ * rounded fp32 operation (fl), and no multiplication is contracted with an addition.  Per line:
+ *
+ * 1. Power.  p[n] = fl(fl(re re) + fl(im im)); re and im are the sample's components converted exactly
+ *    to fp32 (from f32, f16 or int16).
+ * 2. Level.  m = the k-th smallest p[n] of the line, 0-based ascending rank k = floor(Ns rank_pct / 100),
+ *    duplicates counted: an exact order statistic (rank_pct 50 is the median).  p >= +0, so the order of
+ *    the values is the order of their bit patterns.
+ * 3. Flag.  T = fl(alpha m); f[n] = p[n] > T (strict).  alpha is a power ratio.  m = 0 gives T = 0:
+ *    every non-zero sample is flagged.
+ * 4. Dilate.  g[n] = OR of f[j] over |j - n| <= guard, j clipped to the line (no wrap, nothing crosses
+ *    into the next chirp).
+ * 5. Repair every maximal run [a, b] of g by mode:
+ *    FMCW_EXCISE_ZERO    0 over the run.
+ *    FMCW_EXCISE_INTERP  linear between the neighbours lo = x[a-1] and hi = x[b+1], per component in
+ *                        fp32: t = fl(float(n - a + 1) / float(b - a + 2)) (a correctly rounded
+ *                        division), d = fl(hi - lo), out = fl(lo + fl(t d)).  A run that touches one end
+ *                        of the line holds the one neighbour it has (out = lo, or out = hi); a run that
+ *                        covers the whole line is written as zeros.
+ *    The fp32 value is written back in the cube's dtype: f16 rounds to nearest even; int16 rounds half to
+ *    even and cannot saturate (a convex combination of two int16 values); f32 is written as it is.
+ *    Samples outside every run are copied unchanged, bit for bit.
+ * 6. Outputs.
+ *    out_dev     the repaired cube.  It may equal cube_dev (in place); no other overlap is allowed.  In
+ *                place, a line with no flagged sample writes nothing.
+ *    mask_dev    nullable: Ns / 32 words per line, bit n % 32 of word n / 32 = g[n].
+ *    counts_dev  nullable: one word per line [frame][rx][chirp], the samples with g set.
+ *    status_dev  FMCW_EXCISE_STATUS_WORDS (4) words, zeroed by the call itself (a replayed graph starts
+ *                from zero) and complete when the call's kernel ends: [0] samples repaired (the sum of the
+ *                counts), [1] lines with at least one repaired sample, [2] samples flagged before the
+ *                dilation, [3] lines with more than Ns / 2 samples repaired (the level of such a line is
+ *                not to be trusted).  Integer atomics only: the words do not depend on the grid.
+ * Non-finite samples are outside the specification; the call still ends and writes only inside the
+ * caller's buffers. */
+#define FMCW_EXCISE_STATUS_WORDS 4
+typedef enum { FMCW_EXCISE_ZERO = 0, FMCW_EXCISE_INTERP = 1 } fmcw_excise_mode;
+typedef struct fmcw_excise_config {   /* 12 words, 48 bytes */
+  uint32_t n_range;            /* Ns: power of two, 64..8192 */
+  uint32_t n_doppler;          /* chirps per frame, 1..1024 (need not be a power of two) */
+  uint32_t n_rx;               /* 1..64 */
+  int32_t in_dtype;            /* fmcw_in_dtype */
+  int32_t mode;                /* fmcw_excise_mode */
+  uint32_t guard;              /* 0..32 */
+  uint32_t rank_pct;           /* 1..99 */
+  float alpha;                 /* finite, >= 1 */
+  uint32_t max_frames;         /* >= 1; max_frames x n_rx x n_doppler x n_range < 2^32 */
+  int32_t device_id;           /* 0..63 */
+  uint32_t reserved[2];        /* must be 0 */
+} fmcw_excise_config;
+typedef struct fmcw_exciser fmcw_exciser;
+/* Defaults: 1024, 128, 1 rx, F32, ZERO, guard 4, rank_pct 50, alpha 16.0, max_frames 1, device 0. */
+void fmcw_excise_config_default(fmcw_excise_config* cfg);
+/* Validates every field before any device access (FMCW_EINVAL, the message names the field, *out is
+ * NULL), then FMCW_ENODEV as fmcw_cacfar_create.  An exciser owns no device memory. */
+int fmcw_excise_create(const fmcw_excise_config* cfg, fmcw_exciser** out);
+int fmcw_excise_destroy(fmcw_exciser* e);   /* NULL is FMCW_OK */
+/* Device pointers only; stream-ordered, allocates nothing, never synchronises and keeps no state
+ * between calls, so it can be captured into a hipGraph in front of fmcw_enqueue on the same stream and
+ * replayed.  One memset of the status words and one launch: every line is read once and written at most
+ * once.  Arguments are checked before any device access: status_dev, cube_dev and out_dev non-NULL,
+ * n_frames in 1..max_frames, cube_dev and out_dev 16-byte aligned and equal or disjoint. */
+int fmcw_excise_enqueue(fmcw_exciser* e, const void* cube_dev, size_t n_frames, void* out_dev,
+                        uint32_t* mask_dev, uint32_t* counts_dev, uint32_t* status_dev, void* stream);
+/* Test hook: bounds the persistent workgroups, which stride over the lines, so that a small call drives
+ * a workgroup through several lines.  0 = the built-in bound (the workgroups resident at once), else
+ * min(that bound, grid).  Results never depend on it. */
+int fmcw_excise_set_grid_for_test(fmcw_exciser* e, uint32_t grid);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
