@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/fmcw.h"
+#include "spec_rows.hpp"
 
 namespace fmcw {
 
@@ -23,8 +24,8 @@ namespace fmcw {
 // The training window [train_r0, train_r0 + train_rows) of one (frame, rx) plane of
 // [frame][rx][range][chirp] is ONE contiguous run of Cf = train_rows * n_doppler points.  A step is
 // 64 consecutive points of that run in every channel: lane s loads point 64 sb + s of channel k,
-// 512 contiguous bytes per wave and channel (with MTI also its two predecessors in the row, the
-// lines the neighbouring lanes ask for), and writes the two real rows to the wave's LDS tile
+// 512 contiguous bytes per wave and channel (with MTI, spec_rows.hpp's mti_point, also its two
+// predecessors in the row, the lines the neighbouring lanes ask for), and writes the two real rows to the wave's LDS tile
 // [snapshot][ROWS + 1]; the ROWS MFMAs of the step read their operand back transposed, lane l from
 // [KK m + l / ROWS][l % ROWS].  Both the stride-(ROWS+1) write and the contiguous read are free of
 // bank conflicts.  A lane past Cf (the last step of a frame) writes zeros.  There is no branch
@@ -97,26 +98,12 @@ k_adapt_acc(const float2* __restrict__ spec, AdaptGeom g, float* __restrict__ pa
       const bool live = e < g.cf;
       const uint32_t ec = live ? e : 0u;                // a lane past the run loads point 0 and drops it
       const uint32_t c = ec & (g.nd - 1);               // its chirp
-      // no branch around the loads: the channels' loads of a step are in flight together.  The
-      // canceller's predecessors are loaded from a clamped address and dropped before chirp 0.
-      const int b1 = c >= 1 ? 1 : 0, b2 = c >= 2 ? 2 : 0;
+      // no branch around the loads (mti_point's neither): the channels' loads of a step are in
+      // flight together
       const float2* src = spec + (size_t)f * g.nrx * g.rx_step + g.off0 + ec;
 #pragma unroll 8
       for (uint32_t k = 0; k < g.nrx; ++k, src += g.rx_step) {
-        float2 x = *src;
-        if constexpr (MTI >= 2) {  // zero delay line before chirp 0
-          float2 x1 = src[-b1];
-          x1 = b1 ? x1 : make_float2(0.f, 0.f);
-          if constexpr (MTI == 2) {
-            x.x -= x1.x;
-            x.y -= x1.y;
-          } else {
-            float2 x2 = src[-b2];
-            x2 = b2 ? x2 : make_float2(0.f, 0.f);
-            x.x = x.x - 2.f * x1.x + x2.x;
-            x.y = x.y - 2.f * x1.y + x2.y;
-          }
-        }
+        const float2 x = mti_point<MTI>(src, c);
         mine[k] = live ? x.x : 0.f;
         mine[NP + k] = live ? x.y : 0.f;
       }

@@ -5,6 +5,7 @@
 
 #include "cfar1d.hpp"
 #include "fft_device.hpp"
+#include "spec_rows.hpp"
 
 namespace fmcw {
 
@@ -22,8 +23,9 @@ namespace fmcw {
 // Per tile and beam (the streaming form: every beam re-reads the channels' points, from L1 / L2
 // after the first, and the registers do not grow with n_rx):
 //   v[m] = sum_k W[b][k] y_k[m], k = 0 .. n_rx-1 in that order (four fmaf per term: the result
-//   depends on the inputs alone, not on the grid or the wave); y_k the canceller over x_k, its
-//   neighbours x[c-1], x[c-2] loaded directly (the lines the neighbouring lanes just asked for);
+//   depends on the inputs alone, not on the grid or the wave); y_k the canceller over x_k
+//   (spec_rows.hpp's mti_point: its neighbours x[c-1], x[c-2] loaded directly, the lines the
+//   neighbouring lanes just asked for);
 //   W[b][k] is uniform and arrives through the scalar cache;
 //   v[m] *= w[c]; Dft<16>; the LDS rows; the remaining passes with the last one in registers;
 //   |X| -> the wave's LDS region -> 16 B per lane, non-temporal, to maps[f][b][r0..][0..].
@@ -78,18 +80,7 @@ k_beams(const float2* __restrict__ spec, const float2* __restrict__ wts, const f
 #pragma unroll
         for (int m = 0; m < 16; ++m) {
           const int c = t + P * m;
-          float2 x = src[c];
-          if constexpr (MTI >= 2) {  // zero delay line before chirp 0
-            const float2 x1 = c >= 1 ? src[c - 1] : make_float2(0.f, 0.f);
-            if constexpr (MTI == 2) {
-              x.x -= x1.x;
-              x.y -= x1.y;
-            } else {
-              const float2 x2 = c >= 2 ? src[c - 2] : make_float2(0.f, 0.f);
-              x.x = x.x - 2.f * x1.x + x2.x;
-              x.y = x.y - 2.f * x1.y + x2.y;
-            }
-          }
+          const float2 x = mti_point<MTI>(src + c, (uint32_t)c);
           v[m].x = fmaf(-w.y, x.y, fmaf(w.x, x.x, v[m].x));
           v[m].y = fmaf(w.y, x.x, fmaf(w.x, x.y, v[m].y));
         }

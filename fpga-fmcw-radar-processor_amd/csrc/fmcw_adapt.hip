@@ -25,19 +25,11 @@ namespace {
 
 using AccFn = void (*)(const float2*, fmcw::AdaptGeom, float*);
 
-template <int ROWS>
-AccFn pick_mti(int mti) {
-  return mti == FMCW_MTI_OFF      ? fmcw::k_adapt_acc<ROWS, FMCW_MTI_OFF>
-         : mti == FMCW_MTI_2PULSE ? fmcw::k_adapt_acc<ROWS, FMCW_MTI_2PULSE>
-                                  : fmcw::k_adapt_acc<ROWS, FMCW_MTI_3PULSE>;
-}
-
 int validate(const fmcw_adapt_config& c) {
   if (int rc = fmcw::check_map_dims(c.n_range, c.n_doppler)) return rc;
-  if (c.n_rx < 1 || c.n_rx > 16) return fail(FMCW_EINVAL, "n_rx=%u: must be in [1, 16] (17..64 is not built)", c.n_rx);
+  if (int rc = fmcw::check_n_rx(c.n_rx, 16)) return rc;
   if (c.n_beams < 1 || c.n_beams > 64) return fail(FMCW_EINVAL, "n_beams=%u: must be in [1, 64]", c.n_beams);
-  if (c.mti_mode != FMCW_MTI_OFF && c.mti_mode != FMCW_MTI_2PULSE && c.mti_mode != FMCW_MTI_3PULSE)
-    return fail(FMCW_EINVAL, "mti_mode %d (0, 2, 3)", c.mti_mode);
+  if (int rc = fmcw::check_mti_mode(c.mti_mode)) return rc;
   if (c.train_rows < 1 || c.train_rows > c.n_range)
     return fail(FMCW_EINVAL, "train_rows=%u: must be in [1, n_range = %u]", c.train_rows, c.n_range);
   if (c.train_r0 > c.n_range - c.train_rows)
@@ -99,21 +91,21 @@ int fmcw_adapt_create(const fmcw_adapt_config* cfg, const float* a_host, fmcw_ad
   fmcw_adapt* a = new fmcw_adapt();
   a->cfg = *cfg;
   a->rows = cfg->n_rx <= 8 ? 16 : 32;
-  a->acc = a->rows == 16 ? pick_mti<16>(cfg->mti_mode) : pick_mti<32>(cfg->mti_mode);
+  a->acc = fmcw::with_mti(cfg->mti_mode, [a](auto m) -> AccFn {
+    constexpr int M = decltype(m)::value;
+    return a->rows == 16 ? fmcw::k_adapt_acc<16, M> : fmcw::k_adapt_acc<32, M>;
+  });
   a->max_grid = a->grid = fmcw::kAdaptMaxUnits / fmcw::kAdaptWaves;
   const size_t na = (size_t)cfg->n_beams * cfg->n_rx;
   const size_t n_part = (size_t)fmcw::kAdaptMaxUnits * a->rows * a->rows;
-  if (hipMalloc(reinterpret_cast<void**>(&a->a), na * sizeof(float2)) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&a->part), n_part * sizeof(float)) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&a->part2),
-                (size_t)fmcw::kAdaptFoldParts * a->rows * a->rows * sizeof(double)) != hipSuccess) {
-    (void)hipGetLastError();
+  const size_t part2_bytes = (size_t)fmcw::kAdaptFoldParts * a->rows * a->rows * sizeof(double);
+  if (!fmcw::alloc_scratch({fmcw::scratch(a->a, na * sizeof(float2)), fmcw::scratch(a->part, n_part * sizeof(float)),
+                            fmcw::scratch(a->part2, part2_bytes)})) {
     fmcw_adapt_destroy(a);
     return fail(FMCW_ENOMEM, "hipMalloc for the constraint matrix (%zu) and the partial tiles (%zu floats) failed", na,
                 n_part);
   }
-  if (hipMemcpy(a->a, a_host, na * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipGetLastError();
+  if (!fmcw::upload_tables({{a->a, a_host, na * sizeof(float2)}})) {
     fmcw_adapt_destroy(a);
     return fail(FMCW_EHIP, "upload of the constraint matrix failed");
   }
@@ -123,10 +115,7 @@ int fmcw_adapt_create(const fmcw_adapt_config* cfg, const float* a_host, fmcw_ad
 
 int fmcw_adapt_destroy(fmcw_adapt* a) {
   if (!a) return FMCW_OK;
-  hipSetDevice(a->cfg.device_id);
-  if (a->a) hipFree(a->a);
-  if (a->part) hipFree(a->part);
-  if (a->part2) hipFree(a->part2);
+  fmcw::free_scratch(a->cfg.device_id, {a->a, a->part, a->part2});
   delete a;
   return FMCW_OK;
 }

@@ -31,10 +31,7 @@ struct BeamKernel {
 template <int NC>
 BeamKernel pick_mti(int mti) {
   using Gm = fmcw::DopplerGeom<NC>;
-  const BeamFn fn = mti == FMCW_MTI_OFF      ? fmcw::k_beams<NC, FMCW_MTI_OFF>
-                    : mti == FMCW_MTI_2PULSE ? fmcw::k_beams<NC, FMCW_MTI_2PULSE>
-                                             : fmcw::k_beams<NC, FMCW_MTI_3PULSE>;
-  return {fn, Gm::WR, Gm::NT};
+  return {fmcw::with_mti(mti, [](auto m) -> BeamFn { return fmcw::k_beams<NC, decltype(m)::value>; }), Gm::WR, Gm::NT};
 }
 
 BeamKernel pick(uint32_t nd, int mti) {
@@ -50,12 +47,10 @@ BeamKernel pick(uint32_t nd, int mti) {
 
 int validate(const fmcw_beams_config& c) {
   if (int rc = fmcw::check_map_dims(c.n_range, c.n_doppler)) return rc;
-  if (c.n_rx < 1 || c.n_rx > 64) return fail(FMCW_EINVAL, "n_rx=%u: must be in [1, 64]", c.n_rx);
+  if (int rc = fmcw::check_n_rx(c.n_rx, 64)) return rc;
   if (c.n_beams < 1 || c.n_beams > 64) return fail(FMCW_EINVAL, "n_beams=%u: must be in [1, 64]", c.n_beams);
-  if (c.window != FMCW_WIN_NONE && c.window != FMCW_WIN_HAMMING)
-    return fail(FMCW_EINVAL, "window %d: the beamformer has the float windows only (NONE, HAMMING)", c.window);
-  if (c.mti_mode != FMCW_MTI_OFF && c.mti_mode != FMCW_MTI_2PULSE && c.mti_mode != FMCW_MTI_3PULSE)
-    return fail(FMCW_EINVAL, "mti_mode %d (0, 2, 3)", c.mti_mode);
+  if (int rc = fmcw::check_float_window(c.window, "beamformer")) return rc;
+  if (int rc = fmcw::check_mti_mode(c.mti_mode)) return rc;
   if (c.reserved != 0) return fail(FMCW_EINVAL, "reserved %u: must be 0", c.reserved);
   if (int rc = fmcw::check_device_id(c.device_id)) return rc;
   return FMCW_OK;
@@ -104,15 +99,11 @@ int fmcw_beams_create(const fmcw_beams_config* cfg, const float* weights_host, f
   b->cfg = *cfg;
   b->k = pick(nd, cfg->mti_mode);
   b->max_grid = b->grid = fmcw::resident_grid(reinterpret_cast<const void*>(b->k.fn), b->k.NT, 0, prop);
-  if (hipMalloc(reinterpret_cast<void**>(&b->w), nw * sizeof(float2)) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&b->win), nd * sizeof(float)) != hipSuccess) {
-    (void)hipGetLastError();
+  if (!fmcw::alloc_scratch({fmcw::scratch(b->w, nw * sizeof(float2)), fmcw::scratch(b->win, nd * sizeof(float))})) {
     fmcw_beams_destroy(b);
     return fail(FMCW_ENOMEM, "hipMalloc for the beamformer's weights (%zu) and window (%u entries) failed", nw, nd);
   }
-  if (hipMemcpy(b->w, weights_host, nw * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(b->win, win.data(), nd * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipGetLastError();
+  if (!fmcw::upload_tables({{b->w, weights_host, nw * sizeof(float2)}, {b->win, win.data(), nd * sizeof(float)}})) {
     fmcw_beams_destroy(b);
     return fail(FMCW_EHIP, "upload of the beamformer's weights and window failed");
   }
@@ -122,9 +113,7 @@ int fmcw_beams_create(const fmcw_beams_config* cfg, const float* weights_host, f
 
 int fmcw_beams_destroy(fmcw_beams* b) {
   if (!b) return FMCW_OK;
-  hipSetDevice(b->cfg.device_id);
-  if (b->w) hipFree(b->w);
-  if (b->win) hipFree(b->win);
+  fmcw::free_scratch(b->cfg.device_id, {b->w, b->win});
   delete b;
   return FMCW_OK;
 }

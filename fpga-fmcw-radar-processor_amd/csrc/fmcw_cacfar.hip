@@ -122,8 +122,7 @@ int fmcw_cacfar_create(const fmcw_cacfar_config* cfg, fmcw_cacfar** out) {
     return rc;
   }
   c->max_grid = c->grid = fmcw::resident_grid(emit, fmcw::kCaNT, c->lds_bytes, prop);
-  if (hipMalloc(reinterpret_cast<void**>(&c->tile_words), 2 * c->max_tiles * sizeof(uint32_t)) != hipSuccess) {
-    (void)hipGetLastError();
+  if (!fmcw::alloc_scratch({fmcw::scratch(c->tile_words, 2 * c->max_tiles * sizeof(uint32_t))})) {
     const size_t tiles = c->max_tiles;
     delete c;
     return fail(FMCW_ENOMEM, "hipMalloc for the detector's %zu tile words failed", 2 * tiles);
@@ -134,8 +133,7 @@ int fmcw_cacfar_create(const fmcw_cacfar_config* cfg, fmcw_cacfar** out) {
 
 int fmcw_cacfar_destroy(fmcw_cacfar* c) {
   if (!c) return FMCW_OK;
-  hipSetDevice(c->cfg.device_id);
-  if (c->tile_words) hipFree(c->tile_words);
+  fmcw::free_scratch(c->cfg.device_id, {c->tile_words});
   delete c;
   return FMCW_OK;
 }

@@ -97,10 +97,7 @@ void fmcw_cmap_config_default(fmcw_cmap_config* cfg) {
 
 int fmcw_cmap_destroy(fmcw_cmap* c) {
   if (!c) return FMCW_OK;
-  hipSetDevice(c->cfg.device_id);
-  if (c->planes) hipFree(c->planes);
-  if (c->ctl) hipFree(c->ctl);
-  if (c->tile_words) hipFree(c->tile_words);
+  fmcw::free_scratch(c->cfg.device_id, {c->planes, c->ctl, c->tile_words});
   delete c;
   return FMCW_OK;
 }
@@ -141,13 +138,12 @@ int fmcw_cmap_create(const fmcw_cmap_config* cfg, fmcw_cmap** out) {
   }
   c->max_grid = c->grid = fmcw::resident_grid(emit, fmcw::kCmNT, c->lds_bytes, prop);
   const size_t ctl_words = 2 + 2 * (size_t)cfg->n_streams;
-  if (hipMalloc(reinterpret_cast<void**>(&c->planes), 2 * c->plane_floats * sizeof(float)) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&c->ctl), ctl_words * sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&c->tile_words), 2 * c->max_tiles * sizeof(uint32_t)) != hipSuccess) {
-    (void)hipGetLastError();
-    const size_t bytes = 2 * c->plane_floats * sizeof(float) + 2 * c->max_tiles * sizeof(uint32_t);
+  const size_t plane_bytes = 2 * c->plane_floats * sizeof(float), tile_bytes = 2 * c->max_tiles * sizeof(uint32_t);
+  if (!fmcw::alloc_scratch({fmcw::scratch(c->planes, plane_bytes), fmcw::scratch(c->ctl, ctl_words * sizeof(uint32_t)),
+                            fmcw::scratch(c->tile_words, tile_bytes)})) {
     fmcw_cmap_destroy(c);
-    return fail(FMCW_ENOMEM, "hipMalloc for the clutter map's %zu B of planes and tile words failed", bytes);
+    return fail(FMCW_ENOMEM, "hipMalloc for the clutter map's %zu B of planes and tile words failed",
+                plane_bytes + tile_bytes);
   }
   // ages 0, copy 0 current; the planes' contents are irrelevant at age 0
   if (hipMemsetAsync(c->ctl, 0, ctl_words * sizeof(uint32_t), nullptr) != hipSuccess ||

@@ -89,8 +89,7 @@ int fmcw_merge_create(const fmcw_merge_config* cfg, fmcw_merger** out) {
 
 int fmcw_merge_destroy(fmcw_merger* m) {
   if (!m) return FMCW_OK;
-  hipSetDevice(m->cfg.device_id);
-  fmcw::free_scratch({m->masks, m->tile_cnt, m->start});
+  fmcw::free_scratch(m->cfg.device_id, {m->masks, m->tile_cnt, m->start});
   delete m;
   return FMCW_OK;
 }

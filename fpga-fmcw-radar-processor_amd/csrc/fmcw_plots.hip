@@ -128,8 +128,7 @@ int fmcw_plots_create(const fmcw_plots_config* cfg, fmcw_plotter** out) {
 
 int fmcw_plots_destroy(fmcw_plotter* p) {
   if (!p) return FMCW_OK;
-  hipSetDevice(p->cfg.device_id);
-  fmcw::free_scratch({p->masks, p->tile_cnt});
+  fmcw::free_scratch(p->cfg.device_id, {p->masks, p->tile_cnt});
   delete p;
   return FMCW_OK;
 }

@@ -67,9 +67,7 @@ int fmcw_tws_dev_create(const fmcw_tws_dev_config* cfg, fmcw_tws_dev** out) {
   t->cfg = *cfg;
   const size_t state_bytes = (size_t)cfg->n_streams * kStateWords * sizeof(uint32_t);
   const size_t start_bytes = ((size_t)cfg->max_scans * cfg->n_streams + 1) * sizeof(uint32_t);
-  if (hipMalloc(reinterpret_cast<void**>(&t->state), state_bytes) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&t->start), start_bytes) != hipSuccess) {
-    (void)hipGetLastError();
+  if (!fmcw::alloc_scratch({fmcw::scratch(t->state, state_bytes), fmcw::scratch(t->start, start_bytes)})) {
     fmcw_tws_dev_destroy(t);
     return fail(FMCW_ENOMEM, "hipMalloc(%zu + %zu) for the tracker's state and frame index failed", state_bytes,
                 start_bytes);
@@ -86,9 +84,7 @@ int fmcw_tws_dev_create(const fmcw_tws_dev_config* cfg, fmcw_tws_dev** out) {
 
 int fmcw_tws_dev_destroy(fmcw_tws_dev* t) {
   if (!t) return FMCW_OK;
-  hipSetDevice(t->cfg.device_id);
-  if (t->state) hipFree(t->state);
-  if (t->start) hipFree(t->start);
+  fmcw::free_scratch(t->cfg.device_id, {t->state, t->start});
   delete t;
   return FMCW_OK;
 }

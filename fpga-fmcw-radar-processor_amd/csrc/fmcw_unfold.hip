@@ -129,8 +129,7 @@ int fmcw_unfold_create(const fmcw_unfold_config* cfg, fmcw_unfolder** out) {
 
 int fmcw_unfold_destroy(fmcw_unfolder* u) {
   if (!u) return FMCW_OK;
-  hipSetDevice(u->cfg.device_id);
-  fmcw::free_scratch({u->masks, u->tile_cnt, u->tie_cnt, u->folds, u->start, u->vstart});
+  fmcw::free_scratch(u->cfg.device_id, {u->masks, u->tile_cnt, u->tie_cnt, u->folds, u->start, u->vstart});
   delete u;
   return FMCW_OK;
 }

@@ -1,6 +1,6 @@
 // host_util.hip -- the helpers of internal.hpp that the objects beside fmcw_handle share (plotter, bearing
-// estimator, beamformer, cell-averaging detector, device tracker, clutter map, adaptive weights).  Host
-// code only.
+// estimator, beamformer, cell-averaging detector, device tracker, clutter map, adaptive weights, merger,
+// unfolder, exciser).  Host code only.
 #include <cstring>
 
 #include "internal.hpp"
@@ -18,6 +18,22 @@ int check_map_dims(uint32_t n_range, uint32_t n_doppler) {
 int check_device_id(int device_id) {
   if (device_id < 0 || device_id > 63) return fail(FMCW_EINVAL, "device_id %d (0..63)", device_id);
   return FMCW_OK;
+}
+
+int check_n_rx(uint32_t n_rx, uint32_t max) {
+  if (n_rx >= 1 && n_rx <= max) return FMCW_OK;
+  if (max < 64) return fail(FMCW_EINVAL, "n_rx=%u: must be in [1, %u] (%u..64 is not built)", n_rx, max, max + 1);
+  return fail(FMCW_EINVAL, "n_rx=%u: must be in [1, %u]", n_rx, max);
+}
+
+int check_float_window(int window, const char* object) {
+  if (window == FMCW_WIN_NONE || window == FMCW_WIN_HAMMING) return FMCW_OK;
+  return fail(FMCW_EINVAL, "window %d: the %s has the float windows only (NONE, HAMMING)", window, object);
+}
+
+int check_mti_mode(int mti_mode) {
+  if (mti_mode == FMCW_MTI_OFF || mti_mode == FMCW_MTI_2PULSE || mti_mode == FMCW_MTI_3PULSE) return FMCW_OK;
+  return fail(FMCW_EINVAL, "mti_mode %d (0, 2, 3)", mti_mode);
 }
 
 int open_device(int device_id, hipDeviceProp_t* prop) {
@@ -70,9 +86,19 @@ bool alloc_scratch(std::initializer_list<ScratchBuf> bufs) {
   return true;
 }
 
-void free_scratch(std::initializer_list<void*> ptrs) {
+void free_scratch(int device_id, std::initializer_list<void*> ptrs) {
+  hipSetDevice(device_id);
   for (void* p : ptrs)
     if (p) hipFree(p);
+}
+
+bool upload_tables(std::initializer_list<TableUpload> tables) {
+  for (const TableUpload& t : tables)
+    if (hipMemcpy(t.dst, t.src, t.bytes, hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipGetLastError();
+      return false;
+    }
+  return true;
 }
 
 int raise_lds_limit(std::initializer_list<const void*> fns, size_t bytes, const char* name) {

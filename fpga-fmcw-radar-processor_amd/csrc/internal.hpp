@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <initializer_list>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/fmcw.h"
@@ -30,6 +31,19 @@ inline uint32_t clamp_grid(uint32_t grid, uint32_t max_grid) { return grid ? std
 // n_range a power of two in [64, 8192], n_doppler one in [32, 1024]: the maps the stage kernels write
 int check_map_dims(uint32_t n_range, uint32_t n_doppler);
 int check_device_id(int device_id);   // 0..63
+// The configuration checks of the objects on fmcw_range_ct's plain spectrum (bearing estimator,
+// beamformer, adaptive weights).  The interface's n_rx bound is 64; a smaller `max` is what is built.
+int check_n_rx(uint32_t n_rx, uint32_t max);             // 1..max
+int check_float_window(int window, const char* object);  // NONE, HAMMING; "the <object> has ..."
+int check_mti_mode(int mti_mode);                        // fmcw_mti_mode
+// f(std::integral_constant<int, M>{}), M the fmcw_mti_mode of a checked mti_mode: how a run-time mode
+// picks a kernel's MTI instantiation.  f returns the same type for every M.
+template <class F>
+auto with_mti(int mti_mode, F&& f) {
+  if (mti_mode == FMCW_MTI_2PULSE) return f(std::integral_constant<int, FMCW_MTI_2PULSE>{});
+  if (mti_mode == FMCW_MTI_3PULSE) return f(std::integral_constant<int, FMCW_MTI_3PULSE>{});
+  return f(std::integral_constant<int, FMCW_MTI_OFF>{});
+}
 // Makes device_id (>= 0: check_device_id) the current device; FMCW_ENODEV unless it exists and is a
 // gfx950.  *prop, when given, receives its properties.
 int open_device(int device_id, hipDeviceProp_t* prop = nullptr);
@@ -46,7 +60,7 @@ int check_rec_list_args(const void* recs_dev, size_t rec_stride, size_t rec_cap,
 
 // An object's device scratch: alloc_scratch() fills every pointer of the list or returns false with the
 // pending HIP error cleared (the caller then destroys the object and reports FMCW_ENOMEM with its own
-// text); free_scratch() frees those that are set.
+// text); free_scratch() makes the object's device current and frees those that are set.
 struct ScratchBuf {
   void** ptr;
   size_t bytes;
@@ -54,7 +68,15 @@ struct ScratchBuf {
 template <class T>
 ScratchBuf scratch(T*& p, size_t bytes) { return {reinterpret_cast<void**>(&p), bytes}; }
 bool alloc_scratch(std::initializer_list<ScratchBuf> bufs);
-void free_scratch(std::initializer_list<void*> ptrs);
+void free_scratch(int device_id, std::initializer_list<void*> ptrs);
+// The host tables an object copies to its scratch at create (window, twiddles, weights), in list order:
+// false with the pending HIP error cleared (the caller destroys the object and reports FMCW_EHIP).
+struct TableUpload {
+  void* dst;
+  const void* src;
+  size_t bytes;
+};
+bool upload_tables(std::initializer_list<TableUpload> tables);
 
 // The sizes of one call on a record list, for kernels that stride over tiles of `tile` items:
 // cap = min(rec_cap, max_recs) records examined at most; tiles of its cap x items_per_rec items;

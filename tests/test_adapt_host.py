@@ -78,6 +78,31 @@ def test_create_rejects_bad_fields(lib_built, field, value, msg):
     assert not h.value
 
 
+# the fields fmcw_adapt_create checks through the shared helpers, in its order, each between the field
+# checked before it and the one after: (field, bad value, the whole message)
+SHARED_CHECKS = [
+    ("n_doppler", 16, b"n_doppler=16: must be a power of two in [32, 1024]"),
+    ("n_rx", 17, b"n_rx=17: must be in [1, 16] (17..64 is not built)"),
+    ("n_beams", 65, b"n_beams=65: must be in [1, 64]"),
+    ("mti_mode", 1, b"mti_mode 1 (0, 2, 3)"),
+    ("train_rows", 0, b"train_rows=0: must be in [1, n_range = 1024]"),
+]
+
+
+@pytest.mark.parametrize("i", [1, 3])
+def test_shared_checks_keep_their_text_and_order(lib_built, i):
+    """With the field before it bad as well, the earlier message; with the field after it bad as well,
+    its own, byte for byte."""
+    for lo, want in ((i - 1, SHARED_CHECKS[i - 1][2]), (i, SHARED_CHECKS[i][2])):
+        cfg = default_cfg(lib_built)
+        for field, value, _ in SHARED_CHECKS[lo:lo + 2]:
+            setattr(cfg, field, value)
+        a = (C.c_float * (2 * 65 * 17))(*([1.0] * (2 * 65 * 17)))
+        h = C.c_void_p(1)
+        assert lib_built.fmcw_adapt_create(C.byref(cfg), a, C.byref(h)) == L.FMCW_EINVAL
+        assert lib_built.fmcw_last_error() == want and not h.value
+
+
 def test_training_window_inside_the_map(lib_built):
     """[train_r0, train_r0 + train_rows) at the map's last row is accepted as far as the device; one
     row further is FMCW_EINVAL."""

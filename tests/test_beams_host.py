@@ -71,6 +71,32 @@ def test_create_rejects_bad_fields(lib_built, field, value, msg):
     assert not h.value
 
 
+# the fields fmcw_beams_create checks through the shared helpers, in its order, each between the field
+# checked before it and the one after: (field, bad value, the whole message)
+SHARED_CHECKS = [
+    ("n_doppler", 16, b"n_doppler=16: must be a power of two in [32, 1024]"),
+    ("n_rx", 65, b"n_rx=65: must be in [1, 64]"),
+    ("n_beams", 65, b"n_beams=65: must be in [1, 64]"),
+    ("window", L.WIN_Q15_RTL, b"window 2: the beamformer has the float windows only (NONE, HAMMING)"),
+    ("mti_mode", 4, b"mti_mode 4 (0, 2, 3)"),
+    ("reserved", 1, b"reserved 1: must be 0"),
+]
+
+
+@pytest.mark.parametrize("i", [1, 3, 4])
+def test_shared_checks_keep_their_text_and_order(lib_built, i):
+    """With the field before it bad as well, the earlier message; with the field after it bad as well,
+    its own, byte for byte."""
+    for lo, want in ((i - 1, SHARED_CHECKS[i - 1][2]), (i, SHARED_CHECKS[i][2])):
+        cfg = default_cfg(lib_built)
+        for field, value, _ in SHARED_CHECKS[lo:lo + 2]:
+            setattr(cfg, field, value)
+        w = (C.c_float * (2 * 65 * 65))(*([1.0] * (2 * 65 * 65)))
+        h = C.c_void_p(1)
+        assert lib_built.fmcw_beams_create(C.byref(cfg), w, C.byref(h)) == L.FMCW_EINVAL
+        assert lib_built.fmcw_last_error() == want and not h.value
+
+
 @pytest.mark.parametrize("bad", [float("nan"), float("inf"), -float("inf")])
 def test_create_rejects_bad_weights(lib_built, bad):
     cfg = default_cfg(lib_built)

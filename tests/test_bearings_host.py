@@ -169,6 +169,30 @@ def test_create_rejects_bad_fields(lib_built, field, value, msg):
     assert not h.value
 
 
+# the fields fmcw_bearings_create checks through the shared helpers, in its order, each between the field
+# checked before it and the one after: (field, bad value, the whole message)
+SHARED_CHECKS = [
+    ("n_doppler", 16, b"n_doppler=16: must be a power of two in [32, 1024]"),
+    ("n_rx", 65, b"n_rx=65: must be in [1, 64]"),
+    ("window", L.WIN_Q15_RTL, b"window 2: the bearing estimator has the float windows only (NONE, HAMMING)"),
+    ("mti_mode", 1, b"mti_mode 1 (0, 2, 3)"),
+    ("spacing", -0.5, b"spacing -0.5: must be positive and finite (wavelengths)"),
+]
+
+
+@pytest.mark.parametrize("i", [1, 2, 3])
+def test_shared_checks_keep_their_text_and_order(lib_built, i):
+    """With the field before it bad as well, the earlier message; with the field after it bad as well,
+    its own, byte for byte."""
+    for lo, want in ((i - 1, SHARED_CHECKS[i - 1][2]), (i, SHARED_CHECKS[i][2])):
+        cfg = default_cfg(lib_built)
+        for field, value, _ in SHARED_CHECKS[lo:lo + 2]:
+            setattr(cfg, field, value)
+        h = C.c_void_p(1)
+        assert lib_built.fmcw_bearings_create(C.byref(cfg), C.byref(h)) == L.FMCW_EINVAL
+        assert lib_built.fmcw_last_error() == want and not h.value
+
+
 def test_null_and_stride_arguments(lib_built):
     assert lib_built.fmcw_bearings_create(None, None) == L.FMCW_EINVAL
     assert lib_built.fmcw_bearings_destroy(None) == L.FMCW_OK

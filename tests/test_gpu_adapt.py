@@ -114,6 +114,20 @@ def test_windows_frames_and_mti_at_one_shape(gpu, nrx, window, nf, mti):
     check(scene(32, nrx)[:nf], a, loading, mti, r0, rows, f"{NR}x32 rx{nrx} mti{mti} frames{nf} rows[{r0},{r0 + rows})")
 
 
+@pytest.mark.parametrize("nf", AR.FRAMES)
+@pytest.mark.parametrize("nrx", [8, 9])
+def test_training_run_shorter_than_a_step(gpu, nrx, nf):
+    """One training row at n_doppler 32 under the 3-pulse canceller, at the last n_rx of the 16-row tile
+    and the first of the 32-row one.  A frame's run is half a 64-point step: lanes 32 .. 63 fall back to
+    point 0 as chirp 0, where the canceller's predecessor loads are clamped, and must add nothing.  The
+    row is not the map's first, so what lies before its chirp 0 in memory is the previous row's last
+    chirps, which the zero delay line drops."""
+    r0, rows, loading = AR.WINDOWS[1]
+    assert rows * 32 < 64 and r0 > 0
+    a = AR.case_constraints(nrx, 3, seed=nrx + nf)[1]
+    check(scene(32, nrx)[:nf], a, loading, 3, r0, rows, f"{NR}x32 rx{nrx} mti3 frames{nf} rows[{r0},{r0 + rows})")
+
+
 @pytest.mark.parametrize("nb", [1, 3, 64])
 def test_beam_counts(gpu, nb):
     for nrx in (5, 16):

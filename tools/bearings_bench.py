@@ -8,7 +8,7 @@ between two events) and prints one JSON line per (workload, scale override): the
 the records, the bytes of spectrum rows the call reads (records x n_rx x n_doppler x 8) over that
 time, and -- as the yardstick -- the FMCW_K_COMPACT time of the call that produced the list.  Also
 the cost of the extra fmcw_range_ct pass beside fmcw_enqueue alone on the same handle.
-usage: python tools/bearings_bench.py [--cases c3:0,c3:1] [--frames 4] [--iters 20] [--no-snaps]
+usage: python tools/bearings_bench.py [--cases c3:0,c3:1] [--frames 4] [--iters 20] [--no-snaps] [--mti 0|2|3]
 (a case is workload:cfar_scale_ovr; ovr 1 is the reference's dense list, ~27 % of all cells)"""
 import argparse
 import json
@@ -27,6 +27,7 @@ def main():
     ap.add_argument("--frames", type=int, default=4)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--no-snaps", action="store_true", help="pass snaps_dev = NULL")
+    ap.add_argument("--mti", type=int, default=0, choices=[0, 2, 3], help="the estimator's canceller (the list is the path's)")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -76,14 +77,14 @@ def main():
         out = torch.empty((n, 8), dtype=torch.int32, device=dev)
         snaps = None if a.no_snaps else torch.empty((n, nrx, 2), dtype=torch.float32, device=dev)
         st = torch.zeros(2, dtype=torch.int32, device=dev)
-        with BearingEstimator(ns, nc, nrx, max_records=n) as be:
+        with BearingEstimator(ns, nc, nrx, mti=a.mti, max_records=n) as be:
             us = timed(lambda: be.enqueue(spec, F, dets, 16, cap, nd, out, snaps, st, stream=stream), a.iters)
         assert int(st[0].item()) == n and int(st[1].item()) == 0, st
         nu = out[:, 3].view(torch.float32)
         power = out[:, 5].view(torch.float32)
         strong = power > 0.5 * power.max()
         row_bytes = n * nrx * nc * 8
-        print(json.dumps({"workload": w, "ovr": ovr, "frames": F, "n_records": n, "snaps": snaps is not None,
+        print(json.dumps({"workload": w, "ovr": ovr, "frames": F, "n_records": n, "snaps": snaps is not None, "mti": a.mti,
                           "bearings_us_per_call": round(us, 1), "k_compact_us_per_call": round(compact_us, 1),
                           "ratio": round(us / max(compact_us, 1e-9), 2), "ns_per_record": round(1e3 * us / n, 2),
                           "row_bytes": row_bytes, "row_read_GBps": round(row_bytes / us / 1e3, 1),
