@@ -190,3 +190,18 @@ def matrix_case(nd, nrx, mti):
     n_doppler, n_rx and MTI mode."""
     i = DOPPLERS.index(nd) + RXS.index(nrx) + MTIS.index(mti)
     return FRAMES[i % 2], WINDOWS[(i + RXS.index(nrx) // 3) % 3]
+
+
+# ---- the full-scale cases: beams_ref.full_scale_spec, where the canceller's every output is at full scale ----
+FS_NF = 2
+FS_RXS = [4, 16]
+FS_LOADING = 1e-3
+
+
+def full_scale_case(nd, nrx, mti):
+    """(spec, a): 2 frames of white Gaussian cells (the beamformer's full-scale scene: the whole map
+    trains, so every row, frame and chirp of every channel counts in R with the same weight) and 3 random
+    complex constraints."""
+    from beams_ref import full_scale_spec
+    return (full_scale_spec(FS_NF, nrx, NR, nd, seed=9000 + 10 * nd + nrx),
+            case_constraints(nrx, 3, seed=500 + 1000 * nd + 10 * nrx + mti)[1])

@@ -159,3 +159,31 @@ def assert_bearings_match(got, got_snaps, ref, ref_s, ref_a, spacing=0.5, label=
         used["coherence"] = float(frac.max())
         assert used["coherence"] <= 1.0, f"{label} coherence error {used['coherence']:.3f} of its bound"
     return used
+
+
+# ---- the full-scale cases (tests/test_gpu_bearings.py), checked on the CPU by tests/test_bearings_host.py ----
+FS_NF, FS_NR, FS_NRX = 2, 64, 4
+FS_DOPPLERS = [32, 1024]                  # half the wave idle in a 64-chirp step; 16 steps a row
+FS_MTIS = [0, 2, 3]
+FS_BINS = 8                               # records per (frame, range row)
+
+
+def full_scale_records(n_frames, n_range, n_doppler):
+    """A record list (frame / range / doppler) that is no detection list: FS_BINS cells in every range
+    row of every frame, n_doppler / FS_BINS apart, the first one moving on by one bin from row to row
+    and on through the frames, so that the list visits every Doppler bin as well."""
+    step = n_doppler // FS_BINS
+    assert n_frames * n_range >= step
+    f, r, j = np.meshgrid(np.arange(n_frames), np.arange(n_range), np.arange(FS_BINS), indexing="ij")
+    recs = np.zeros(f.size, np.dtype([("frame", "<u4"), ("range", "<u2"), ("doppler", "<u2"),     # fmcw.DET_DTYPE
+                                      ("mag", "<f4"), ("threshold", "<f4")]))
+    recs["frame"], recs["range"] = f.ravel(), r.ravel()
+    recs["doppler"] = (j * step + (r + n_range * f) % step).ravel()
+    return recs
+
+
+def full_scale_case(nc, mti):
+    """(spec, recs, win): beams_ref.full_scale_spec with the list above; the window alternates."""
+    from beams_ref import full_scale_spec
+    win = ("hamming", "none")[(FS_DOPPLERS.index(nc) + FS_MTIS.index(mti)) % 2]
+    return full_scale_spec(FS_NF, FS_NRX, FS_NR, nc, seed=8000 + nc), full_scale_records(FS_NF, FS_NR, nc), win

@@ -243,6 +243,21 @@ def test_gpu_inputs_are_within_the_bound(nd):
     assert worst <= AR.W_BOUND_MAX
 
 
+@pytest.mark.parametrize("nd", AR.DOPPLERS)
+def test_full_scale_inputs_are_within_the_bound(nd):
+    """The full-scale cases of tests/test_gpu_adapt.py on the reference alone: white noise gives a
+    well-conditioned covariance, so no fallback, and the bound on W far under W_BOUND_MAX."""
+    for nrx in AR.FS_RXS:
+        for mti in AR.MTIS:
+            spec, a = AR.full_scale_case(nd, nrx, mti)
+            ref = AR.adapt_ref(spec, a, float(np.float32(AR.FS_LOADING)), mti)
+            wb = AR.w_bound(ref, AR.gamma(AR.FS_NF, AR.NR, nd))
+            print(f"\nfull scale {AR.NR}x{nd} rx{nrx} mti{mti}: cond(Rl) {np.linalg.cond(ref['Rl']):.3g}, "
+                  f"bound on W {wb:.3g} relative")
+            assert ref["flags"] == 0 and ref["K"] == AR.FS_NF * AR.NR * nd
+            assert np.linalg.cond(ref["Rl"]) < 10.0 and wb <= AR.W_BOUND_MAX
+
+
 def test_chain_length():
     assert AR.chain_length(1, 1, 32) == (64, 1)            # half a step
     assert AR.chain_length(1, 3, 32) == (64, 2) and AR.chain_length(3, 3, 32) == (64, 6)

@@ -248,3 +248,169 @@ def test_cli_beams_arguments(capsys, tmp_path):
     with pytest.raises(SystemExit):                                      # rejected before any device access
         cli.main([str(tmp_path / "one_rx.npy"), "--n-range", "64", "--n-doppler", "32", "--beams", "4"])
     assert "multi-rx" in capsys.readouterr().err
+
+
+# ---- what the tolerance leaves unchecked: the scenes the GPU cases run on ---------------------------------
+SHARE_CAP = 0.02
+FS_CASES = ([(nc, nrx, mti, R.FS_NB) for nc in R.FS_DOPPLERS for nrx in R.FS_RXS for mti in R.FS_MTIS] +
+            [(32, nrx, 0, nb) for nrx, nb in R.FS_LIMITS])
+
+
+def fmt_shares(sh):
+    return ", ".join(f"{k} {100 * v:.3f} %" for k, v in sh.items())
+
+
+@pytest.mark.parametrize("nc,nrx,mti,nb", FS_CASES)
+def test_full_scale_scene_is_checked_in_every_cell(nc, nrx, mti, nb):
+    """On every full-scale case of tests/test_gpu_beams.py a map of zeros, the reference one range row
+    off and the reference of the next frame or beam each pass assert_maps_match's bounds in at most
+    2 % of the cells (what is left is the canceller's null at Doppler 0, and chance).  Measured on the
+    reference alone, before any GPU value."""
+    spec, w, win = R.full_scale_case(nc, nrx, mti, nb)
+    assert spec.dtype == np.complex64 and spec.shape == (R.FS_NF, nrx, R.FS_NR, nc)
+    rms = np.sqrt(np.mean(spec.real.astype(np.float64) ** 2)), np.sqrt(np.mean(spec.imag.astype(np.float64) ** 2))
+    assert np.allclose(rms, R.FULL_SCALE_RMS, rtol=0.05), rms
+    sh = R.unchecked_shares(*R.beams_ref(spec, w, win, mti))
+    print(f"\nfull scale {R.FS_NR}x{nc} rx{nrx} beams{nb} mti{mti} {win}: passes unnoticed in {fmt_shares(sh)}")
+    assert max(sh.values()) <= SHARE_CAP, sh
+
+
+def two_targets_case(nc, nrx=4, nr=64, nf=R.FS_NF, seed=40):
+    """The scene of the GPU cases before the full-scale one: synth's two_targets through the oracle's
+    range stage (fmcw_oracle.range_ct, fp64) as the host stand-in for fmcw_range_ct, rounded to the
+    complex64 the GPU stage writes; 3 random beams."""
+    cube = synth.frames(nf, nr, nc, nrx, "two_targets", seed=seed, rx_phase=[0.25, -0.125])
+    spec = O.range_ct(cube).astype(np.complex64)
+    rng = np.random.default_rng(seed)
+    w = (rng.standard_normal((3, nrx)) + 1j * rng.standard_normal((3, nrx))).astype(np.complex64)
+    return spec, w
+
+
+def test_two_targets_scene_is_unchecked_in_most_cells():
+    """Why the full-scale scene exists: on two_targets at 64 x 1024 with MTI off a map of zeros passes
+    both bounds in more than 90 % of the cells."""
+    spec, w = two_targets_case(1024)
+    sh = R.unchecked_shares(*R.beams_ref(spec, w, "hamming", 0))
+    print(f"\ntwo_targets 64x1024 rx4 beams3 mti0 hamming: passes unnoticed in {fmt_shares(sh)}")
+    assert sh["zero"] > 0.90, sh
+
+
+def test_unchecked_share_counts_both_bounds():
+    """unchecked_share on a hand-made pair: a cell passes when it is within 1e-4 of the map's largest
+    scale and, above 1e-3 of that scale, within 1e-4 of its own."""
+    ref = np.array([[[[1000.0, 500.0, 0.5, 0.05]]]])
+    S = ref.copy()
+    assert R.unchecked_share(ref, S, ref) == 1.0
+    assert R.unchecked_share(ref, S, 0.0) == 0.25                    # only 0.05 is below 1e-4 * 1000
+    other = ref + np.array([0.09, 0.06, 0.09, 0.09])                # 0.06 > 1e-4 * 500: the per-bin bound
+    assert R.unchecked_share(ref, S, other) == 0.75
+    assert R.unchecked_share(ref, S, ref + 0.11) == 0.0              # the peak bound, everywhere
+    S2 = np.array([[[[1000.0, 500.0, 2.0, 0.05]]]])                  # 2.0 > 1e-3 * 1000: now held to 2e-4
+    assert R.unchecked_share(ref, S2, other) == 0.5
+
+
+# ---- a catalogue of kernel defects, modelled on the reference ------------------------------------------
+def model(spec, w, win, mti, *, delay="zero", keep_x2_at_chirp_1=False, win_shift=0):
+    """beams_ref's maps with the canceller's edge and the window open to a defect."""
+    x = np.einsum("bk,fkrc->fbrc", np.asarray(w).astype(np.complex128), np.asarray(spec).astype(np.complex128))
+    nc = x.shape[-1]
+
+    def delayed(k):
+        if delay == "zero":
+            return R._delayed(x, k)
+        flat = x.reshape(x.shape[:2] + (-1,))                         # the row before it in memory
+        return R._delayed(flat, k).reshape(x.shape)
+    m1, m2 = R.MTI_COEF[mti]
+    x1, x2 = delayed(1), delayed(2)
+    if keep_x2_at_chirp_1:
+        x2[..., 1] = x[..., 1]                                         # the clamped load's value, not dropped
+    y = x - m1 * x1 + m2 * x2
+    return np.abs(np.fft.fft(y * np.roll(R.window(nc, win), win_shift), axis=-1))
+
+
+def defect_row(spec, w, win, mti):
+    m = model(spec, w, win, mti)
+    m[-1, :, -1] = m[-1, :, -2]
+    return m
+
+
+def defect_frame(spec, w, win, mti):
+    m = model(spec, w, win, mti)
+    m[1:] = m[0]
+    return m
+
+
+# name -> (the defective maps, the MTI modes in which the defect changes anything)
+DEFECTS = {
+    "one row of the last tile taken from the row before": (defect_row, (0, 2, 3)),
+    "frame f > 0 computed from frame 0": (defect_frame, (0, 2, 3)),
+    "beam b > 0 accumulated onto beam b-1's sum":
+        (lambda s, w, win, mti: model(s, np.cumsum(np.asarray(w, np.complex128), axis=0), win, mti), (0, 2, 3)),
+    "the delay line before chirp 0 taken from the preceding row":
+        (lambda s, w, win, mti: model(s, w, win, mti, delay="memory"), (2, 3)),
+    "x[c-2] not dropped at chirp 1": (lambda s, w, win, mti: model(s, w, win, mti, keep_x2_at_chirp_1=True), (3,)),
+    "a conjugated weight": (lambda s, w, win, mti: model(s, np.conj(w), win, mti), (0, 2, 3)),
+    "the last channel left out":
+        (lambda s, w, win, mti: model(s, np.concatenate([w[:, :-1], 0 * w[:, -1:]], 1), win, mti), (0, 2, 3)),
+    "the window shifted by one chirp": (lambda s, w, win, mti: model(s, w, win, mti, win_shift=1), (0, 2, 3)),
+}
+
+
+def seen(defect, spec, w, mti):
+    """(whether assert_maps_match tells the defective maps, rounded to the fp32 a kernel writes, from
+    the reference; the share of the cells the defect changes in which a bound is exceeded)."""
+    ref, S = R.beams_ref(spec, w, "hamming", mti)
+    bad = defect(spec, w, "hamming", mti).astype(np.float32)
+    changed = bad != ref.astype(np.float32)
+    assert changed.any()
+    caught = changed & ~R.passes(ref, S, bad)
+    assert caught.any() == (max(R.bounds_used(bad, ref, S).values()) > 1.0)
+    return bool(caught.any()), caught.sum() / changed.sum()
+
+
+def test_the_defect_model_without_a_defect_is_the_reference():
+    spec, w, _ = R.full_scale_case(32, 4, 3)
+    for win in ("hamming", "none"):
+        for mti in (0, 2, 3):
+            assert np.array_equal(model(spec, w, win, mti), R.beams_ref(spec, w, win, mti)[0])
+
+
+@pytest.mark.parametrize("name", list(DEFECTS))
+@pytest.mark.parametrize("nc", [32, 1024])
+def test_full_scale_scene_rejects_the_defect(nc, name):
+    """Each defect, in every MTI mode in which it changes anything (Hamming, 4 rx, 3 random beams,
+    2 frames), fails assert_maps_match on the full-scale scene."""
+    defect, mtis = DEFECTS[name]
+    for mti in mtis:
+        spec, w, _ = R.full_scale_case(nc, 4, mti)
+        rejected, share = seen(defect, spec, w, mti)
+        print(f"\nfull scale 64x{nc} mti{mti}: {name}: out of bound in {100 * share:.1f} % of the cells it changes")
+        assert rejected, f"{name}: passes at n_doppler {nc}, mti {mti}"
+        with pytest.raises(AssertionError):
+            R.assert_maps_match(defect(spec, w, "hamming", mti).astype(np.float32), *R.beams_ref(spec, w, "hamming", mti))
+
+
+@pytest.mark.parametrize("nc", [32, 1024])
+def test_which_defects_the_two_targets_scene_lets_through(nc):
+    """The same catalogue on the two_targets scene.  Information, not an assertion: which defects the
+    scene of the other GPU cases lets through under the same bounds, and in how few of the cells a
+    defect changes it is seen at all (a defect confined to the other cells passes)."""
+    spec, w = two_targets_case(nc)
+    print()
+    for name, (defect, mtis) in DEFECTS.items():
+        for mti in mtis:
+            rejected, share = seen(defect, spec, w, mti)
+            print(f"two_targets 64x{nc} mti{mti}: {name}: {'rejected' if rejected else 'PASSES UNNOTICED'}, "
+                  f"out of bound in {100 * share:.2f} % of the cells it changes")
+
+
+@pytest.mark.parametrize("nc,nrx,mti,nb", FS_CASES)
+def test_float32_evaluation_of_the_full_scale_cases(nc, nrx, mti, nb):
+    """beams_ref.beams_f32 (the specification in float32 on the CPU) against the fp64 reference: the
+    fractions of the two bounds that rounding alone uses, for DESIGN.md 4c to set beside the GPU's.
+    The peak bound is asserted with a wide margin; the per-bin figure is printed (a matrix DFT's
+    rounding is not the kernel's)."""
+    spec, w, win = R.full_scale_case(nc, nrx, mti, nb)
+    used = R.bounds_used(R.beams_f32(spec, w, win, mti), *R.beams_ref(spec, w, win, mti))
+    print(f"\nfloat32 on the CPU, {R.FS_NR}x{nc} rx{nrx} beams{nb} mti{mti} {win}: peak {used['peak']:.3g}, bin {used['bin']:.3g}")
+    assert used["peak"] <= 0.05

@@ -85,6 +85,28 @@ def test_power_is_the_oracle_map_cell(geom, mti):
     assert np.abs(out["power"] - want).max() <= 1e-9 * o["mag"].max()
 
 
+@pytest.mark.parametrize("mti", R.FS_MTIS)
+@pytest.mark.parametrize("nc", R.FS_DOPPLERS)
+def test_full_scale_list_visits_every_row_and_bin(nc, mti):
+    """The full-scale cases of tests/test_gpu_bearings.py on the reference alone: the list holds every
+    (frame, range row) 8 times and every Doppler bin, and the reference rounded to the record's fp32
+    fields passes assert_bearings_match -- so at most 5 % of the list is ill-conditioned for nu (white
+    cells have no preferred phase slope, and the canceller's null takes the records at Doppler 0)."""
+    spec, recs, win = R.full_scale_case(nc, mti)
+    assert len(recs) == R.FS_NF * R.FS_NR * R.FS_BINS
+    rows = set(zip(recs["frame"].tolist(), recs["range"].tolist()))
+    assert len(rows) == R.FS_NF * R.FS_NR and set(recs["doppler"].tolist()) == set(range(nc))
+    ref, s, a = R.bearings_ref(spec, recs, win=win, mti=mti)
+    got = np.zeros(len(recs), BEARING_DTYPE)
+    for k in ("frame", "range", "doppler", "flags", "nu", "power", "coherence"):
+        got[k] = ref[k]
+    got["sin_theta"] = got["nu"] * np.float32(2.0)
+    used = R.assert_bearings_match(got, s.astype(np.complex64), ref, s, a, label="the reference against itself")
+    print(f"\nfull scale {R.FS_NR}x{nc} rx{R.FS_NRX} mti{mti} {win}: {len(recs)} records, {used['skipped']} "
+          f"ill-conditioned for nu, worst E_P / |P| among the rest {used['cond']:.3g}")
+    assert used["s"] <= 0.05 and used["power"] <= 0.05
+
+
 def test_detections_of_two_targets_sit_at_a_quarter_cycle():
     cube = synth.frame(64, 32, 4, "two_targets", seed=1234)
     o = O.process(cube, O.Cfar1D())

@@ -6,7 +6,9 @@ from the kernel's add chains); every comparison prints the worst f
 Shapes (adapt_ref): n_range 64; n_doppler 32 and 1024; n_rx 1, 2, 3, 4, 5, 8, 9, 15, 16 (8 | 9 is the
 boundary between the 16-row and the 32-row accumulator tile); 1 and 3 frames; the whole map, one row
 and three rows as training windows (2 and 6 units at n_doppler 32: no multiple of the 4 waves of a
-workgroup); MTI off, 2- and 3-pulse; 1, 3 and 64 beams.
+workgroup); MTI off, 2- and 3-pulse; 1, 3 and 64 beams.  The full-scale cases run on the beamformer's
+white Gaussian scene (adapt_ref.full_scale_case), where every unit of the accumulation weighs the same.
+enqueue_checked also fails on any word of W or cov that still holds the sentinel.
 """
 import functools
 
@@ -21,7 +23,7 @@ from fmcw import (ADAPT_FALLBACK, DET_DTYPE, AdaptiveWeights, BeamFormer, Device
                   steering_vectors, steering_weights)
 from fmcw import _lib as L
 from fmcw.adapt import INFO_WORDS, parse_info
-from test_gpu_beams import run as run_beams
+from test_gpu_beams import assert_all_written, run as run_beams
 from test_gpu_r05 import _Hip
 
 pytestmark = pytest.mark.gpu
@@ -56,6 +58,9 @@ def enqueue_checked(ad, dspec, n_frames, want_cov=True):
         assert np.all(raw[n:] == SENTINEL), f"bytes after {name} were written"
     if not want_cov:
         assert np.all(raws[1] == SENTINEL), "cov_dev is NULL but cov was written"
+    else:
+        assert_all_written(raws[1][:sizes[1]], "cov")
+    assert_all_written(raws[0][:sizes[0]], "w")
     W = raws[0][:sizes[0]].view(np.complex64).reshape(c.n_beams, c.n_rx).copy()
     R = raws[1][:sizes[1]].view(np.complex128).reshape(c.n_rx, c.n_rx).copy()
     words = raws[2][:sizes[2]].view(np.uint32).copy()
@@ -100,6 +105,18 @@ def test_against_reference(gpu, nd, nrx, mti):
                   f"{NR}x{nd} rx{nrx} mti{mti} frames{nf} rows[{r0},{r0 + rows}) {name}", dspec)
     finally:
         dspec.free()
+
+
+@pytest.mark.parametrize("mti", AR.MTIS)
+@pytest.mark.parametrize("nrx", AR.FS_RXS)
+@pytest.mark.parametrize("nd", AR.DOPPLERS)
+def test_full_scale_against_reference(gpu, nd, nrx, mti):
+    """The beamformer's full-scale scene (white Gaussian cells, 2 frames, the whole map as the training
+    window): every row, frame and chirp weighs the same in R, so a unit left out, taken twice or
+    cancelled against the wrong predecessor moves cov by about 1 / n_units of its scale, against a bound
+    of gamma.  tests/test_adapt_host.py: the reference takes no fallback here."""
+    spec, a = AR.full_scale_case(nd, nrx, mti)
+    check(spec, a, AR.FS_LOADING, mti, 0, NR, f"full scale {NR}x{nd} rx{nrx} mti{mti} frames{AR.FS_NF}")
 
 
 @pytest.mark.parametrize("mti", AR.MTIS)

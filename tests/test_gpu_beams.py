@@ -7,6 +7,13 @@ Shapes: n_range 64 with every n_doppler 32 .. 1024 (each its own kernel instanti
 radix; 2 .. 64 wave tiles per frame); n_rx 1..4; 1, 3 and 8 beams; MTI off, 2- and 3-pulse; Hamming
 and no window; 3 frames (two_targets at rx_phase 0.25 / -0.125, random_target at 0.25, two_targets
 again), so that at n_doppler 32 the 6 wave tiles are no multiple of a workgroup's 4.
+
+On those scenes (a few tones over weak noise) nearly every map cell lies below 1e-4 of the map's largest
+scale, where a zero or another row's value passes (tests/test_beams_host.py measures it).  The
+full-scale cases run on beams_ref.full_scale_spec instead, a white Gaussian spectrum from the host on
+which the same bounds hold every cell: every n_doppler x n_rx 1, 4 x MTI, n_rx 64 and n_beams 64, and
+the capped grids.  run() also fails on any map word that still holds the sentinel the buffer was
+filled with (as a float it is -2.9e-16, a zero for the tolerance).
 """
 import functools
 from types import SimpleNamespace
@@ -17,12 +24,14 @@ import pytest
 import fmcw_oracle as O
 from fmcw import DET_DTYPE, BeamFormer, DeviceBuffer, RadarCore, cli, formats, steering_weights, synth
 from fmcw import _lib as L
+import beams_ref as BR
 from beams_ref import assert_maps_match, beams_ref
 from test_gpu_r05 import _Hip
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = 0xA5
+SENTINEL_WORD = 0xA5A5A5A5    # as a float32 -2.9e-16: finite, and a zero for any tolerance
 TAIL = 4096       # sentinel bytes kept after the last map
 NF = 3
 NR = 64
@@ -62,9 +71,16 @@ def scene(nc, nrx, nr=NR):
     return SimpleNamespace(cube=cube, spec=spec, nr=nr, nc=nc, nrx=nrx)
 
 
+def assert_all_written(raw, what):
+    """No 32-bit word of a float output (its bytes, a multiple of 4) still holds the sentinel the buffer
+    was filled with.  A genuine value with that bit pattern is -2.9e-16, which no scene here produces."""
+    left = np.flatnonzero(np.ascontiguousarray(raw).view(np.uint32) == SENTINEL_WORD)
+    assert left.size == 0, f"{what}: {left.size} words were never written, the first at word {left[0]}"
+
+
 def run(bf, spec, n_frames=None):
     """One fmcw_beams_enqueue on a host spectrum into a sentinel-filled buffer: the maps, after checking
-    that the TAIL bytes behind the last map kept the sentinel."""
+    that the TAIL bytes behind the last map kept the sentinel and that every map cell was written."""
     n_frames = len(spec) if n_frames is None else n_frames
     c = bf.cfg
     nbytes = n_frames * bf.maps_frame_bytes()
@@ -77,6 +93,7 @@ def run(bf, spec, n_frames=None):
     dspec.free()
     dm.free()
     assert np.all(raw[nbytes:] == SENTINEL), "bytes after the last map were written"
+    assert_all_written(raw[:nbytes], "maps")
     return raw[:nbytes].view(np.float32).reshape(n_frames, c.n_beams, c.n_range, c.n_doppler).copy()
 
 
@@ -175,6 +192,57 @@ def test_grid_independence(gpu, nc, nrx, mti):
         for grid in (1, 3, 0):
             bf.set_grid_for_test(grid)
             assert run(bf, sc.spec).tobytes() == base.tobytes(), grid
+
+
+# ---- the full-scale scene: white Gaussian cells, so that the bounds hold every map cell -------------------
+@functools.lru_cache(maxsize=None)
+def full_scale(nc, nrx, mti, nb=BR.FS_NB):
+    """(spec, weights, win, ref, S) of beams_ref.full_scale_case: a spectrum from the host, no range FFT.
+    tests/test_beams_host.py shows on the reference alone that a zero, the neighbouring row and the
+    next frame's or beam's map pass in at most 2 % of these cells."""
+    spec, w, win = BR.full_scale_case(nc, nrx, mti, nb)
+    ref, S = beams_ref(spec, w, win=win, mti=mti)
+    for a in (w, ref, S):
+        a.setflags(write=False)
+    return spec, w, win, ref, S
+
+
+@pytest.mark.parametrize("mti", BR.FS_MTIS)
+@pytest.mark.parametrize("nrx", BR.FS_RXS)
+@pytest.mark.parametrize("nc", BR.FS_DOPPLERS)
+def test_full_scale_against_reference(gpu, nc, nrx, mti):
+    """2 frames, 3 beams of random complex weights, every n_doppler (many rows per wave at 32, one row
+    per tile at 1024): a wrong tile-to-row or tile-to-frame mapping, a sum carried over between beams or
+    a wrong canceller edge is out of bound wherever it falls."""
+    spec, w, win, ref, S = full_scale(nc, nrx, mti)
+    with BeamFormer(NR, nc, nrx, w, window=win, mti=mti) as bf:
+        got = run(bf, spec)
+    assert_maps_match(got, ref, S, label=f"full scale {NR}x{nc} rx{nrx} beams{BR.FS_NB} mti{mti} {win}")
+
+
+@pytest.mark.parametrize("nrx,nb", BR.FS_LIMITS)
+def test_full_scale_at_the_header_limits(gpu, nrx, nb):
+    """n_rx 64 and n_beams 64, the largest the header allows, at 64 x 32."""
+    spec, w, win, ref, S = full_scale(32, nrx, 0, nb)
+    with BeamFormer(NR, 32, nrx, w, window=win) as bf:
+        got = run(bf, spec)
+    assert_maps_match(got, ref, S, label=f"full scale {NR}x32 rx{nrx} beams{nb} mti0 {win}")
+
+
+@pytest.mark.parametrize("nc,nrx,mti", [(32, 4, 0), (1024, 1, 2), (32, 1, 3), (1024, 4, 3)])
+def test_full_scale_grid_independence(gpu, nc, nrx, mti):
+    """1 and 3 workgroups through the hook, then the built-in grid again, on the full-scale scene: a
+    workgroup's later tiles, frames and beams are held to the reference in every cell, and not only to
+    the first run's bytes."""
+    spec, w, win, ref, S = full_scale(nc, nrx, mti)
+    with BeamFormer(NR, nc, nrx, w, window=win, mti=mti) as bf:
+        base = run(bf, spec)
+        assert_maps_match(base, ref, S, label=f"full scale {NR}x{nc} rx{nrx} mti{mti} {win} built-in grid")
+        for grid in (1, 3, 0):
+            bf.set_grid_for_test(grid)
+            got = run(bf, spec)
+            assert_maps_match(got, ref, S, label=f"full scale {NR}x{nc} rx{nrx} mti{mti} {win} grid {grid}")
+            assert got.tobytes() == base.tobytes(), grid
 
 
 def test_graph_replay_on_a_second_cube(gpu):

@@ -5,7 +5,10 @@ fmcw_range_ct output downloaded to the host.  The tolerances are bearings_ref.as
 
 Shapes: n_range 64 with n_doppler 32 (fewer chirps than lanes), 64 (one per lane) and 128, and
 128 x 1024 (a lane takes 16 chirps and d * c reaches its largest value); n_rx 1..4; MTI off, 2- and
-3-pulse; Hamming and no window; 2 frames (one of each synthetic recipe).
+3-pulse; Hamming and no window; 2 frames (one of each synthetic recipe).  The full-scale cases take
+records in every range row and Doppler bin of a white Gaussian spectrum (bearings_ref.full_scale_case),
+not at detections.  run() also fails on any word of the records or snapshots written that still holds
+the sentinel.
 """
 import functools
 from types import SimpleNamespace
@@ -16,7 +19,9 @@ import pytest
 import fmcw_oracle as O
 from fmcw import (BEARING_DTYPE, DET_DTYPE, PLOT_DTYPE, BearingEstimator, DeviceBuffer, PlotExtractor, RadarCore, cli,
                   formats, synth)
+import bearings_ref as BR
 from bearings_ref import assert_bearings_match, bearings_ref
+from test_gpu_beams import assert_all_written
 from test_gpu_r05 import _Hip
 
 pytestmark = pytest.mark.gpu
@@ -100,10 +105,12 @@ def run(be, spec, n_frames, recs, rec_cap=None, n_word=None, snaps=True):
     k = int(st[0])
     assert k <= slots - 4
     raw = db.download(np.uint8, (slots * 32,))
+    assert_all_written(raw[: k * 32], "bearings")
     got, rest = raw[: k * 32].view(BEARING_DTYPE).copy(), raw[k * 32:]
     sn = sn_rest = None
     if snaps:
         raw = dsn.download(np.uint8, (slots * nrx * 8,))
+        assert_all_written(raw[: k * nrx * 8], "snapshots")
         sn, sn_rest = raw[: k * nrx * 8].view(np.complex64).reshape(k, nrx).copy(), raw[k * nrx * 8:]
     for b in bufs:
         b.free()
@@ -152,6 +159,22 @@ def test_against_reference(gpu, nr, nc, nrx, mti):
         # both recipes place their targets a quarter cycle per element apart
         strong = got["power"] > 0.5 * got["power"].max()
         assert np.all(np.abs(got["nu"][strong] - 0.25) < 0.01) and np.all(got["coherence"][strong] > 0.99)
+
+
+@pytest.mark.parametrize("mti", BR.FS_MTIS)
+@pytest.mark.parametrize("nc", BR.FS_DOPPLERS)
+def test_full_scale_against_reference(gpu, nc, mti):
+    """Records that are no detections: 8 cells in every range row of both frames of the beamformer's
+    full-scale scene (white Gaussian cells from the host), every Doppler bin among them.  Every row's
+    snapshot is then at the scale of its bound, where a detection list visits the targets' rows alone:
+    a wrong row, frame or channel stride, or a wrong canceller edge, is out of bound wherever it falls.
+    tests/test_bearings_host.py: the reference alone leaves at most 12 of the 1024 records to the 5 % a
+    case may skip for nu."""
+    spec, recs, win = BR.full_scale_case(nc, mti)
+    assert recs.dtype == DET_DTYPE
+    sc = SimpleNamespace(spec=spec, nr=BR.FS_NR, nc=nc, nrx=BR.FS_NRX, mti=mti, win=win)
+    got, sn = check(sc, recs, f"full scale {BR.FS_NR}x{nc} rx{BR.FS_NRX} mti{mti} {win}", n_frames=BR.FS_NF)
+    assert not np.any(got["flags"] & 6)
 
 
 @pytest.mark.parametrize("win", ["hamming", "none"])
