@@ -1405,7 +1405,7 @@ def check_case_map(c: Cfg, got, ref):
     """The map rule of a whole-path case: check_map (1e-4 per frame and per significant bin) on
     the fp32 and S48 spectra, the stated 2e-3 per frame on the fp16 spectrum."""
     from conftest import rel_err
-    from test_gpu_parity import check_map
+    from gpu_support import check_map
     if c.spectrum == "f16":
         for f in range(ref.shape[0]):
             e = rel_err(got[f], ref[f])

@@ -12,6 +12,9 @@ merged plot per peak, in list order.
 """
 import numpy as np
 
+from fmcw import DET_DTYPE
+from tile_edge import thin_to
+
 MPLOT_REF_DTYPE = np.dtype([("frame", "<u4"), ("range", "<u2"), ("doppler", "<u2"), ("mag", "<f4"),
                             ("beam", "<u2"), ("n_merged", "<u2"), ("sum_mag", "<f8"),
                             ("d_beam", "<f8"), ("d_range", "<f8"), ("d_doppler", "<f8")])
@@ -145,3 +148,21 @@ def hand_records(rows, dtype):
     for i, (m, r, d, mag) in enumerate(sorted(rows)):
         a["frame"][i], a["range"][i], a["doppler"][i], a["mag"][i] = m, r, d, mag
     return a
+
+
+# ---- list generators of the host and the GPU tests ----
+def random_list(seed, n_maps, nr, nd, density, dtype=DET_DTYPE, levels=5):
+    rng = np.random.default_rng(seed)
+    f, r, d = np.nonzero(rng.random((n_maps, nr, nd)) < density)
+    a = np.zeros(len(f), dtype)
+    a["frame"], a["range"], a["doppler"] = f, r, d
+    a["mag"] = rng.integers(1, levels + 1, len(f)).astype(np.float32)
+    return a
+
+
+def tile_edge_list(n):
+    """Exactly n records of 32 x 32 maps whose last record is in frame 3: merged as 2 scans x 3 beams,
+    maps 4 and 5 are empty."""
+    recs = thin_to(random_list(40, 4, 32, 32, 0.7), n, n)
+    assert len(recs) == n and recs["frame"][-1] == 3, (len(recs), n, int(recs["frame"][-1]))
+    return recs

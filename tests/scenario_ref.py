@@ -24,7 +24,7 @@ import tws_dev_ref as R
 from fmcw import synth
 from plots_ref import plots_ref
 
-MAP_TOL = 1e-4            # BASELINE.json north star (test_gpu_parity.MAP_TOL)
+MAP_TOL = 1e-4            # BASELINE.json north star (gpu_support.MAP_TOL)
 NEAR = 1e-4               # a cell this close (relative) to its threshold may be decided either way
 MTI_MODES = (0, 2, 3)
 PATHS = ("float", "int")

@@ -128,12 +128,13 @@ def test_python_class(lib_built):
 
 # ---- the specification's properties ----
 
-def rayleigh(shape, seed, scale=1.0):
-    return np.random.default_rng(seed).rayleigh(scale, shape).astype(np.float32)
+def noise(shape, seed):
+    """Writable Rayleigh(1) noise of any shape (gpu_support.rayleigh is the cached, read-only 3-D one)."""
+    return np.random.default_rng(seed).rayleigh(1.0, shape).astype(np.float32)
 
 
 def test_first_scan_initialises_and_warmup_holds_detections_back():
-    maps = rayleigh((6, 16, 32), 1)
+    maps = noise((6, 16, 32), 1)
     maps[:, 5, 7] = [1, 1, 1, 50, 60, 70]
     dets, planes, ages = R.detect(maps[:1], warmup=1)
     assert len(dets) == 0 and ages.tolist() == [1]
@@ -151,14 +152,14 @@ def test_first_scan_initialises_and_warmup_holds_detections_back():
 
 
 def test_constant_map_converges_to_itself_and_never_detects():
-    m = rayleigh((16, 32), 2)
+    m = noise((16, 32), 2)
     maps = np.broadcast_to(m, (20, 16, 32))
     for alpha in (1.0, 2.5):
         dets, planes, ages = R.detect(maps, alpha=alpha, warmup=1)
         assert len(dets) == 0                                  # x = c <= M <= alpha M: never x > T
         assert planes[0].tobytes() == m.tobytes() and ages.tolist() == [20]
     # from another start the recurrence contracts towards the map: |c' - x| <= (1 - g) |c - x| up to rounding
-    start = (rayleigh((1, 16, 32), 3), np.array([5], np.uint32))
+    start = (noise((1, 16, 32), 3), np.array([5], np.uint32))
     _, planes, _ = R.detect(maps, gain=0.5, warmup=100, state=start)
     assert np.abs(planes[0] - m).max() <= np.abs(start[0][0] - m).max() * 0.5 ** 20 + 4 * np.finfo(np.float32).eps * m.max()
 
@@ -182,7 +183,7 @@ def test_clip_bounds_the_growth_per_scan():
 
 
 def test_splitting_the_calls_changes_nothing():
-    maps = rayleigh((12, 16, 32), 4)
+    maps = noise((12, 16, 32), 4)
     kw = dict(n_streams=2, alpha=1.5, clip=3.0, floor=0.25, spread=(2, 3), warmup=2)
     whole, planes, ages = R.detect(maps, **kw)
     assert len(whole) > 0 and ages.tolist() == [6, 6]
@@ -210,7 +211,7 @@ def test_neighbourhood_clips_in_range_and_wraps_in_doppler():
     assert {tuple(x) for x in np.argwhere(m == 5.0)} == {(r, d) for r in (0, 1) for d in (31, 0, 1)}   # no row -1 -> 7
     assert {tuple(x) for x in np.argwhere(m == 7.0)} == {(r, d) for r in (6, 7) for d in (30, 31, 0)}
     brute = np.zeros_like(c)
-    c2 = rayleigh((8, 32), 5)
+    c2 = noise((8, 32), 5)
     for r in range(8):
         for d in range(32):
             brute[r, d] = max(c2[rr, (d + dd) % 32] for rr in range(max(r - 2, 0), min(r + 2, 7) + 1) for dd in range(-3, 4))
@@ -237,7 +238,7 @@ def test_clutter_edge_target():
     nr, nd, edge, warm, amp = 1024, 32, 133, 8, 14.0
     tr, td = edge + 2, 9
     scale = np.where(np.arange(nr) < edge, 4.0, 1.0).astype(np.float32)[None, :, None]
-    maps = rayleigh((warm + 1, nr, nd), 20) * scale
+    maps = noise((warm + 1, nr, nd), 20) * scale
     maps[warm, tr, td] = amp
     cm, _, ages = R.detect(maps, alpha=5.0, warmup=warm)
     ca = CA.detect(maps[warm], "ca", alpha=8.0)

@@ -23,12 +23,10 @@ from fmcw import (ADAPT_FALLBACK, DET_DTYPE, AdaptiveWeights, BeamFormer, Device
                   steering_vectors, steering_weights)
 from fmcw import _lib as L
 from fmcw.adapt import INFO_WORDS, parse_info
-from test_gpu_beams import assert_all_written, run as run_beams
-from test_gpu_r05 import _Hip
+from gpu_support import SENTINEL, Hip, assert_all_written, assert_sentinel_after, range_ct_spectrum, run_beams, sentinel_buffer
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5
 TAIL = 256        # sentinel bytes kept after each output
 NR = AR.NR
 
@@ -38,24 +36,18 @@ def scene(nd, nrx):
     return AR.noise_scene(nd, nrx)
 
 
-def sentinel_buffer(nbytes):
-    d = DeviceBuffer(nbytes + TAIL)
-    d.upload(np.full(nbytes + TAIL, SENTINEL, np.uint8))
-    return d
-
-
 def enqueue_checked(ad, dspec, n_frames, want_cov=True):
     """One fmcw_adapt_enqueue on a device spectrum into sentinel-filled buffers: (W, R, info, raw bytes
     of the three outputs), after checking that the bytes behind every output kept the sentinel."""
     c = ad.cfg
     sizes = (ad.w_bytes(), ad.cov_bytes(), 4 * INFO_WORDS)
-    bufs = [sentinel_buffer(n) for n in sizes]
+    bufs = [sentinel_buffer(n + TAIL) for n in sizes]
     ad.enqueue(dspec, n_frames, bufs[0], bufs[1] if want_cov else None, bufs[2])
     raws = [b.download(np.uint8, (n + TAIL,)) for b, n in zip(bufs, sizes)]
     for b in bufs:
         b.free()
     for raw, n, name in zip(raws, sizes, ("w", "cov", "info")):
-        assert np.all(raw[n:] == SENTINEL), f"bytes after {name} were written"
+        assert_sentinel_after(raw, n, 1, name)
     if not want_cov:
         assert np.all(raws[1] == SENTINEL), "cov_dev is NULL but cov was written"
     else:
@@ -199,7 +191,7 @@ def test_null_cov_and_zero_frames(gpu):
         W, _, info, _ = run(ad, spec)
         W2, _, info2, _ = run(ad, spec, want_cov=False)
         assert W.tobytes() == W2.tobytes() and info == info2
-        d = sentinel_buffer(TAIL)
+        d = sentinel_buffer(2 * TAIL)
         ad.enqueue(d, 0, d, d, d)
         assert lib.fmcw_adapt_enqueue(ad._h, None, 0, None, None, None, None) == L.FMCW_OK
         assert lib.fmcw_adapt_enqueue(ad._h, None, 1, d.ptr, None, d.ptr, None) == L.FMCW_EINVAL
@@ -267,7 +259,7 @@ def test_chain_captured_and_replayed_on_a_second_scene(gpu):
     scenes = [(AR.JAM_NU_J, AR.jammer_scene()), (0.42, AR.jammer_scene(seed=8, nu_j=0.42))]
     a = steering_vectors(nrx, [AR.JAM_NU_T])
     wc = steering_weights(nrx, [AR.JAM_NU_T])
-    hip = _Hip()
+    hip = Hip()
     with AdaptiveWeights(nr, nc, nrx, a, loading=1e-2) as ad, BeamFormer(nr, nc, nrx, wc) as bf, \
             RadarCore(N_RANGE=nr, N_DOPPLER=nc, N_RX=1, cfar="os2d", max_frames=1) as core:
         dspec = DeviceBuffer(scenes[0][1].nbytes)
@@ -275,36 +267,32 @@ def test_chain_captured_and_replayed_on_a_second_scene(gpu):
         dm = DeviceBuffer(bf.maps_frame_bytes())
         cap = nr * nc
         dd, dn = DeviceBuffer(cap * 16), DeviceBuffer(16)
-        s = hip.stream()
 
-        def calls():
+        def calls(s):
             ad.enqueue(dspec, 1, dw, dr, di, stream=s.value)
             bf.set_weights_dev(dw, stream=s.value)
             bf.enqueue(dspec, 1, dm, stream=s.value)
             core.cfar(dm, 1, dd, cap, dn, stream=s.value)
-        g, exe = hip.capture(s, calls)
         try:
-            seen = []
-            for nu_j, spec in scenes:
-                dspec.upload(spec)
-                hip.replay(exe, s)
-                W = dw.download(np.complex64, (1, nrx))
-                R = dr.download(np.complex128, (nrx, nrx))
-                info = parse_info(di.download(np.uint32, (INFO_WORDS,)))
-                ref = adapt_ref(spec, a, float(np.float32(1e-2)))
-                assert_matches(W, R, info, ref, gamma(1, nr, nc), 1e-2, f"replay, jammer at {nu_j}")
-                maps = dm.download(np.float32, (1, 1, nr, nc))
-                assert_maps_match(maps, *beams_ref(spec, ref["W"]), label=f"replay map, jammer at {nu_j}")
-                n = int(dn.download(np.uint32, (4,))[0])
-                assert AR.JAM_CELL in os2d_cells(dd.download(DET_DTYPE, (n,)))
-                aj = steering_vectors(nrx, [nu_j])[0].astype(np.complex128)
-                assert abs(W[0].astype(np.complex128) @ aj) <= 10 ** -1.5 * abs(wc[0].astype(np.complex128) @ aj)
-                seen.append(W.tobytes())
-            assert seen[0] != seen[1]
+            with hip.graph(calls) as (exe, s):
+                seen = []
+                for nu_j, spec in scenes:
+                    dspec.upload(spec)
+                    hip.replay(exe, s)
+                    W = dw.download(np.complex64, (1, nrx))
+                    R = dr.download(np.complex128, (nrx, nrx))
+                    info = parse_info(di.download(np.uint32, (INFO_WORDS,)))
+                    ref = adapt_ref(spec, a, float(np.float32(1e-2)))
+                    assert_matches(W, R, info, ref, gamma(1, nr, nc), 1e-2, f"replay, jammer at {nu_j}")
+                    maps = dm.download(np.float32, (1, 1, nr, nc))
+                    assert_maps_match(maps, *beams_ref(spec, ref["W"]), label=f"replay map, jammer at {nu_j}")
+                    n = int(dn.download(np.uint32, (4,))[0])
+                    assert AR.JAM_CELL in os2d_cells(dd.download(DET_DTYPE, (n,)))
+                    aj = steering_vectors(nrx, [nu_j])[0].astype(np.complex128)
+                    assert abs(W[0].astype(np.complex128) @ aj) <= 10 ** -1.5 * abs(wc[0].astype(np.complex128) @ aj)
+                    seen.append(W.tobytes())
+                assert seen[0] != seen[1]
         finally:
-            hip.lib.hipGraphExecDestroy(exe)
-            hip.lib.hipGraphDestroy(g)
-            hip.lib.hipStreamDestroy(s)
             for b in (dspec, dw, dr, di, dm, dd, dn):
                 b.free()
 
@@ -336,10 +324,9 @@ def test_solve_and_cli(gpu, tmp_path):
     4-channel cube writes the beam detections of the chain run by hand (range_ct -> adapt ->
     set_weights_dev -> beams -> cfar) and leaves the plain detection file as it is without it."""
     from fmcw import synth
-    from test_gpu_beams import range_ct
     nc, nrx, nb = 64, 4, 4
     cube = np.ascontiguousarray(synth.frames(2, NR, nc, nrx, "two_targets", seed=40, rx_phase=[0.25, -0.125]))
-    spec = range_ct(cube, NR, nc, nrx)
+    spec = range_ct_spectrum(cube, NR, nc, nrx)
     nus = (np.arange(nb) - nb // 2) / nb
     with AdaptiveWeights(NR, nc, nrx, steering_vectors(nrx, nus), loading=0.05) as ad, \
             BeamFormer(NR, nc, nrx, steering_weights(nrx, nus)) as bf:

@@ -26,13 +26,11 @@ from fmcw import DET_DTYPE, BeamFormer, DeviceBuffer, RadarCore, cli, formats, s
 from fmcw import _lib as L
 import beams_ref as BR
 from beams_ref import assert_maps_match, beams_ref
-from test_gpu_r05 import _Hip
+from gpu_support import SENTINEL, Hip, range_ct_spectrum as range_ct, run_beams as run
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5
-SENTINEL_WORD = 0xA5A5A5A5    # as a float32 -2.9e-16: finite, and a zero for any tolerance
-TAIL = 4096       # sentinel bytes kept after the last map
+TAIL = 4096       # sentinel bytes in the buffers of the tests of calls that must write nothing
 NF = 3
 NR = 64
 DOPPLERS = [32, 64, 128, 256, 512, 1024]
@@ -47,20 +45,6 @@ def three_frame_cube(nr, nc, nrx, seed=40):
         synth.frames(1, nr, nc, nrx, "two_targets", seed=seed + 2, rx_phase=PHASES)]))
 
 
-def range_ct(cube, nr, nc, nrx, win="hamming"):
-    """fmcw_range_ct's spectrum of `cube` on the host (the core is the one the CLI builds)."""
-    nf = len(cube)
-    with RadarCore(N_RANGE=nr, N_DOPPLER=nc, N_RX=nrx, cfar="os1d", max_frames=nf, window=win) as core:
-        dc = DeviceBuffer(cube.nbytes)
-        dc.upload(cube)
-        ds = DeviceBuffer(nf * nrx * nr * nc * 8)
-        core.range_ct(dc, ds, nf)
-        spec = ds.download(np.complex64, (nf, nrx, nr, nc))
-        dc.free()
-        ds.free()
-    return spec
-
-
 @functools.lru_cache(maxsize=None)
 def scene(nc, nrx, nr=NR):
     cube = three_frame_cube(nr, nc, nrx)
@@ -69,32 +53,6 @@ def scene(nc, nrx, nr=NR):
     for a in (cube, spec):
         a.setflags(write=False)
     return SimpleNamespace(cube=cube, spec=spec, nr=nr, nc=nc, nrx=nrx)
-
-
-def assert_all_written(raw, what):
-    """No 32-bit word of a float output (its bytes, a multiple of 4) still holds the sentinel the buffer
-    was filled with.  A genuine value with that bit pattern is -2.9e-16, which no scene here produces."""
-    left = np.flatnonzero(np.ascontiguousarray(raw).view(np.uint32) == SENTINEL_WORD)
-    assert left.size == 0, f"{what}: {left.size} words were never written, the first at word {left[0]}"
-
-
-def run(bf, spec, n_frames=None):
-    """One fmcw_beams_enqueue on a host spectrum into a sentinel-filled buffer: the maps, after checking
-    that the TAIL bytes behind the last map kept the sentinel and that every map cell was written."""
-    n_frames = len(spec) if n_frames is None else n_frames
-    c = bf.cfg
-    nbytes = n_frames * bf.maps_frame_bytes()
-    dspec = DeviceBuffer(max(spec.nbytes, 8))
-    dspec.upload(spec)
-    dm = DeviceBuffer(nbytes + TAIL)
-    dm.upload(np.full(nbytes + TAIL, SENTINEL, np.uint8))
-    bf.enqueue(dspec, n_frames, dm)
-    raw = dm.download(np.uint8, (nbytes + TAIL,))
-    dspec.free()
-    dm.free()
-    assert np.all(raw[nbytes:] == SENTINEL), "bytes after the last map were written"
-    assert_all_written(raw[:nbytes], "maps")
-    return raw[:nbytes].view(np.float32).reshape(n_frames, c.n_beams, c.n_range, c.n_doppler).copy()
 
 
 def check(sc, weights, win, mti, label):
@@ -252,32 +210,28 @@ def test_graph_replay_on_a_second_cube(gpu):
     nc, nrx, nb = 64, 4, 3
     cubes = [three_frame_cube(NR, nc, nrx, seed=40), three_frame_cube(NR, nc, nrx, seed=60)]
     w = case_weights(nrx, nb, seed=3)[1]
-    hip = _Hip()
+    hip = Hip()
     with RadarCore(N_RANGE=NR, N_DOPPLER=nc, N_RX=nrx, cfar="none", max_frames=NF) as core, \
             BeamFormer(NR, nc, nrx, w) as bf:
         dc = DeviceBuffer(cubes[0].nbytes)
         ds = DeviceBuffer(NF * bf.spec_frame_bytes())
         dm = DeviceBuffer(NF * bf.maps_frame_bytes())
-        s = hip.stream()
 
-        def calls():
+        def calls(s):
             core.range_ct(dc, ds, NF, stream=s.value)
             bf.enqueue(ds, NF, dm, stream=s.value)
-        g, exe = hip.capture(s, calls)
         try:
-            seen = []
-            for k in (0, 1):
-                dc.upload(cubes[k])
-                hip.replay(exe, s)
-                spec = ds.download(np.complex64, (NF, nrx, NR, nc))
-                got = dm.download(np.float32, (NF, nb, NR, nc))
-                assert_maps_match(got, *beams_ref(spec, w), label=f"replay {k}")
-                seen.append(got.tobytes())
-            assert seen[0] != seen[1]
+            with hip.graph(calls) as (exe, s):
+                seen = []
+                for k in (0, 1):
+                    dc.upload(cubes[k])
+                    hip.replay(exe, s)
+                    spec = ds.download(np.complex64, (NF, nrx, NR, nc))
+                    got = dm.download(np.float32, (NF, nb, NR, nc))
+                    assert_maps_match(got, *beams_ref(spec, w), label=f"replay {k}")
+                    seen.append(got.tobytes())
+                assert seen[0] != seen[1]
         finally:
-            hip.lib.hipGraphExecDestroy(exe)
-            hip.lib.hipGraphDestroy(g)
-            hip.lib.hipStreamDestroy(s)
             for b in (dc, ds, dm):
                 b.free()
 

@@ -21,12 +21,10 @@ from fmcw import (BEARING_DTYPE, DET_DTYPE, PLOT_DTYPE, BearingEstimator, Device
                   formats, synth)
 import bearings_ref as BR
 from bearings_ref import assert_bearings_match, bearings_ref
-from test_gpu_beams import assert_all_written
-from test_gpu_r05 import _Hip
+from gpu_support import SENTINEL, Hip, assert_all_written
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5
 NF = 2
 MAX_LIST = 300    # detections kept per case (every k-th of the path's list): the reference is O(n n_rx n_doppler)
 
@@ -346,31 +344,27 @@ def test_graph_replay_on_a_second_list(gpu):
     lists = [sc.recs[:37], sc.recs[37:90][::-1].copy()]
     assert len(lists[1]) == 53
     cap = 64
-    hip = _Hip()
+    hip = Hip()
     with estimator(sc) as be:
         dspec = DeviceBuffer(sc.spec.nbytes)
         dspec.upload(sc.spec)
         drec, dn = DeviceBuffer(cap * 16), DeviceBuffer(4)
         db, dsn, dst = DeviceBuffer(cap * 32), DeviceBuffer(cap * sc.nrx * 8), DeviceBuffer(8)
-        s = hip.stream()
-        g, exe = hip.capture(s, lambda: be.enqueue(dspec, NF, drec, 16, cap, dn, db, dsn, dst, stream=s.value))
         try:
-            seen = []
-            for k in (0, 1, 0):
-                recs = lists[k]
-                drec.upload(recs)
-                dn.upload(np.array([len(recs)], np.uint32))
-                hip.replay(exe, s)
-                assert list(dst.download(np.uint32, (2,))) == [len(recs), 0]
-                got = db.download(BEARING_DTYPE, (len(recs),))
-                sn = dsn.download(np.complex64, (len(recs), sc.nrx))
-                assert_bearings_match(got, sn, *bearings_ref(sc.spec, recs, n_frames=NF), label=f"replay {k}")
-                seen.append(got.tobytes())
-            assert seen[0] == seen[2] and seen[0] != seen[1]
+            with hip.graph(lambda s: be.enqueue(dspec, NF, drec, 16, cap, dn, db, dsn, dst, stream=s.value)) as (exe, s):
+                seen = []
+                for k in (0, 1, 0):
+                    recs = lists[k]
+                    drec.upload(recs)
+                    dn.upload(np.array([len(recs)], np.uint32))
+                    hip.replay(exe, s)
+                    assert list(dst.download(np.uint32, (2,))) == [len(recs), 0]
+                    got = db.download(BEARING_DTYPE, (len(recs),))
+                    sn = dsn.download(np.complex64, (len(recs), sc.nrx))
+                    assert_bearings_match(got, sn, *bearings_ref(sc.spec, recs, n_frames=NF), label=f"replay {k}")
+                    seen.append(got.tobytes())
+                assert seen[0] == seen[2] and seen[0] != seen[1]
         finally:
-            hip.lib.hipGraphExecDestroy(exe)
-            hip.lib.hipGraphDestroy(g)
-            hip.lib.hipStreamDestroy(s)
             for b in (dspec, drec, dn, db, dsn, dst):
                 b.free()
 

@@ -8,52 +8,24 @@ the window matrix (one tile per frame, two steps of 32 rows); n_range 64 with ev
 rows just outside them); 8192 x 32 for a strip of 2048 rows (64 steps through the rings); 5 frames of
 256 x 64 under 1 and 2 workgroups for the persistent loop.
 """
-import functools
-
 import numpy as np
 import pytest
 
 import cacfar_ref as R
 from fmcw import DET_DTYPE, BeamFormer, CaCfar, DeviceBuffer, PlotExtractor, RadarCore, steering_weights, synth
 from fmcw import _lib as L
-from test_gpu_r05 import _Hip
+from gpu_support import SENTINEL, Hip, rayleigh, run_map_detector
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5
 CANARY = 8          # sentinel records kept after the list
 DEFAULT = ((4, 4), (1, 2))
-
-
-@functools.lru_cache(maxsize=None)
-def rayleigh(nf, nr, nd, seed):
-    m = np.random.default_rng(seed).rayleigh(1.0, (nf, nr, nd)).astype(np.float32)
-    m.setflags(write=False)
-    return m
 
 
 def run(det, maps, det_cap=None, null_dets=False):
     """One fmcw_cacfar_enqueue on host maps: (the records written, the four status words), after
     checking that every record from min(found, det_cap) on kept the sentinel."""
-    maps = np.ascontiguousarray(maps, np.float32)
-    nf = maps.shape[0]
-    cap = maps.size if det_cap is None else det_cap
-    dm = DeviceBuffer(max(maps.nbytes, 16))
-    dm.upload(maps)
-    dd = DeviceBuffer((cap + CANARY) * 16)
-    dd.upload(np.full((cap + CANARY) * 16, SENTINEL, np.uint8))
-    dn = DeviceBuffer(16)
-    dn.upload(np.full(16, SENTINEL, np.uint8))
-    try:
-        det.enqueue(dm, nf, None if null_dets else dd, cap, dn)
-        st = dn.download(np.uint32, (4,))
-        raw = dd.download(np.uint8, ((cap + CANARY) * 16,))
-    finally:
-        for b in (dm, dd, dn):
-            b.free()
-    n = min(int(st[0]), cap)
-    assert np.all(raw[n * 16:] == SENTINEL), "records after the list were written"
-    return raw[:n * 16].view(DET_DTYPE).copy(), st
+    return run_map_detector(det, maps, det_cap, null_dets, canary=CANARY)
 
 
 def check(maps, mode="ca", ref=DEFAULT[0], guard=DEFAULT[1], alpha=4.0, label=""):
@@ -222,14 +194,13 @@ def test_graph_replay_after_the_map(gpu):
     cubes = [np.ascontiguousarray(synth.frames(nf, nr, nd, 1, "two_targets", seed=71)),
              np.ascontiguousarray(synth.frames(nf, nr, nd, 1, "random_target", seed=72))]
     cap = nf * nr * nd
-    hip = _Hip()
+    hip = Hip()
     with RadarCore(N_RANGE=nr, N_DOPPLER=nd, cfar="none", max_frames=nf) as core, \
             CaCfar(nr, nd, mode="so", alpha=3.0, max_frames=nf) as det:
         dc, dm = DeviceBuffer(cubes[0].nbytes), DeviceBuffer(nf * nr * nd * 4)
         dd, dn = DeviceBuffer(cap * 16), DeviceBuffer(16)
-        s = hip.stream()
 
-        def calls():
+        def calls(s):
             core.enqueue(dc, nf, dm, stream=s.value)
             det.enqueue(dm, nf, dd, cap, dn, stream=s.value)
 
@@ -240,22 +211,19 @@ def test_graph_replay_after_the_map(gpu):
             assert st.tolist() == [len(want), 0, 0, 0] and len(want) > 0
             assert dd.download(DET_DTYPE, (len(want),)).tobytes() == want.tobytes()
             return want.tobytes()
-        g, exe = hip.capture(s, calls)
         try:
-            dc.upload(cubes[0])
-            hip.replay(exe, s)
-            first = result()
-            dc.upload(cubes[1])
-            calls()                                       # a direct call between the replays
-            hip.ok(hip.lib.hipStreamSynchronize(s))
-            direct = result()
-            dn.upload(np.zeros(4, np.uint32))
-            hip.replay(exe, s)
-            assert result() == direct != first
+            with hip.graph(calls) as (exe, s):
+                dc.upload(cubes[0])
+                hip.replay(exe, s)
+                first = result()
+                dc.upload(cubes[1])
+                calls(s)                                      # a direct call between the replays
+                hip.ok(hip.lib.hipStreamSynchronize(s))
+                direct = result()
+                dn.upload(np.zeros(4, np.uint32))
+                hip.replay(exe, s)
+                assert result() == direct != first
         finally:
-            hip.lib.hipGraphExecDestroy(exe)
-            hip.lib.hipGraphDestroy(g)
-            hip.lib.hipStreamDestroy(s)
             for b in (dc, dm, dd, dn):
                 b.free()
 

@@ -8,53 +8,24 @@ rows, the halo rows of a neighbour tile, the clipped halo at rows 0 and 63 and t
 gives 32 tiles of 256 rows; 256 x 64 and 256 x 1024 with 2 streams give 4 and 64 (stream, tile) units for
 the persistent loop.
 """
-import functools
-
 import numpy as np
 import pytest
 
 import cmap_ref as R
 from fmcw import DET_DTYPE, BeamFormer, ClutterMap, DeviceBuffer, PlotExtractor, RadarCore, steering_weights, synth
 from fmcw import _lib as L
-from test_gpu_r05 import _Hip
+from gpu_support import SENTINEL, Hip, rayleigh, run_map_detector
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5
 CANARY = 8          # sentinel records kept after the list
 AGE_MAX = R.AGE_MAX
 
 
-@functools.lru_cache(maxsize=None)
-def rayleigh(nf, nr, nd, seed):
-    m = np.random.default_rng(seed).rayleigh(1.0, (nf, nr, nd)).astype(np.float32)
-    m.setflags(write=False)
-    return m
-
-
 def run(cm, maps, det_cap=None, null_dets=False):
-    """One fmcw_cmap_enqueue on host maps: (the records written, the four status words), after checking
-    that every record from min(found, det_cap) on kept the sentinel."""
-    maps = np.ascontiguousarray(maps, np.float32)
-    nf = maps.shape[0]
-    cap = maps.size if det_cap is None else det_cap
-    dm = DeviceBuffer(max(maps.nbytes, 16))
-    if maps.nbytes:
-        dm.upload(maps)
-    dd = DeviceBuffer((cap + CANARY) * 16)
-    dd.upload(np.full((cap + CANARY) * 16, SENTINEL, np.uint8))
-    dn = DeviceBuffer(16)
-    dn.upload(np.full(16, SENTINEL, np.uint8))
-    try:
-        cm.enqueue(dm, nf, None if null_dets else dd, cap, dn)
-        st = dn.download(np.uint32, (4,))
-        raw = dd.download(np.uint8, ((cap + CANARY) * 16,))
-    finally:
-        for b in (dm, dd, dn):
-            b.free()
-    n = min(int(st[0]), cap)
-    assert np.all(raw[n * 16:] == SENTINEL), "records after the list were written"
-    return raw[:n * 16].view(DET_DTYPE).copy(), st
+    """One fmcw_cmap_enqueue on host maps: (the records written, the four status words), after
+    checking that every record from min(found, det_cap) on kept the sentinel."""
+    return run_map_detector(cm, maps, det_cap, null_dets, canary=CANARY)
 
 
 def same_state(cm, planes, ages):
@@ -277,7 +248,7 @@ def test_state_calls(gpu):
     set_state into a fresh object continues identically; ages saturate at 0xFFFFFFFF."""
     maps = rayleigh(8, 64, 32, 51)
     kw = dict(alpha=1.3, warmup=2)
-    hip = _Hip()
+    hip = Hip()
     with ClutterMap(64, 32, max_frames=4, **kw) as cm, ClutterMap(64, 32, max_frames=4, **kw) as fresh:
         s = hip.stream()
         dm = DeviceBuffer(maps.nbytes)
@@ -331,14 +302,13 @@ def test_graph_replay_after_the_map(gpu):
     cubes = [np.ascontiguousarray(synth.frames(nf, nr, nd, 1, rec, seed=seed)) for rec, seed in recipes]
     kw = dict(alpha=1.5, warmup=1)
     cap = nf * nr * nd
-    hip = _Hip()
+    hip = Hip()
     with RadarCore(N_RANGE=nr, N_DOPPLER=nd, cfar="none", max_frames=nf) as core, \
             ClutterMap(nr, nd, max_frames=nf, **kw) as cm:
         dc, dm = DeviceBuffer(cubes[0].nbytes), DeviceBuffer(nf * nr * nd * 4)
         dd, dn = DeviceBuffer(cap * 16), DeviceBuffer(16)
-        s = hip.stream()
 
-        def calls():
+        def calls(s):
             core.enqueue(dc, nf, dm, stream=s.value)
             cm.enqueue(dm, nf, dd, cap, dn, stream=s.value)
 
@@ -353,24 +323,21 @@ def test_graph_replay_after_the_map(gpu):
             assert st.tolist() == [len(want), 0, 0, 0]
             assert dd.download(DET_DTYPE, (len(want),)).tobytes() == want.tobytes()
             counts.append(len(want))
-        g, exe = hip.capture(s, calls)
         try:
-            for i, cube in enumerate(cubes):
-                dc.upload(cube)
-                dn.upload(np.full(16, SENTINEL, np.uint8))
-                if i == 2:
-                    calls()                                   # a direct call between the replays
-                    hip.ok(hip.lib.hipStreamSynchronize(s))
-                else:
-                    hip.replay(exe, s)
-                result()
-            assert counts[0] > 0 and min(counts[1:]) > 0      # the first call's scan 0 only initialises
-            assert state[0][1].tolist() == [2 * len(cubes)]
-            same_state(cm, *state[0])
+            with hip.graph(calls) as (exe, s):
+                for i, cube in enumerate(cubes):
+                    dc.upload(cube)
+                    dn.upload(np.full(16, SENTINEL, np.uint8))
+                    if i == 2:
+                        calls(s)                                  # a direct call between the replays
+                        hip.ok(hip.lib.hipStreamSynchronize(s))
+                    else:
+                        hip.replay(exe, s)
+                    result()
+                assert counts[0] > 0 and min(counts[1:]) > 0      # the first call's scan 0 only initialises
+                assert state[0][1].tolist() == [2 * len(cubes)]
+                same_state(cm, *state[0])
         finally:
-            hip.lib.hipGraphExecDestroy(exe)
-            hip.lib.hipGraphDestroy(g)
-            hip.lib.hipStreamDestroy(s)
             for b in (dc, dm, dd, dn):
                 b.free()
 

@@ -15,11 +15,10 @@ import pytest
 import excise_ref as R
 from fmcw import DeviceBuffer, InterferenceExciser, RadarCore, synth
 from fmcw import _lib as L
-from test_gpu_r05 import _Hip
+from gpu_support import SENTINEL, Hip
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5
 CANARY = 256         # sentinel bytes kept after every output
 DTYPES = ("f32", "f16", "i16")
 
@@ -285,13 +284,12 @@ def test_graph_replay_in_front_of_the_chain(gpu):
     included."""
     clean, dirty, truth = e2e_cubes()
     nr, nd, cap = 256, 64, 4096
-    hip = _Hip()
+    hip = Hip()
     with InterferenceExciser(nr, nd, mode=R.INTERP) as ex, RadarCore(N_RANGE=nr, N_DOPPLER=nd, cfar="os2d") as core:
         dc, dm, dk, dn = filled(dirty.nbytes), filled(nr * nd * 4), filled(nd * 4), filled(nr // 8 * nd)
         dd, ds, dst = filled(cap * 16), filled(16), filled(16)
-        s = hip.stream()
 
-        def calls():
+        def calls(s):
             ex.enqueue(dc, 1, dc, dn, dk, dst, stream=s.value)
             core.enqueue(dc, 1, dm, dd, cap, ds, stream=s.value)
 
@@ -308,22 +306,19 @@ def test_graph_replay_in_front_of_the_chain(gpu):
             return (dc.download(np.uint8, (dirty.nbytes,)).tobytes(), dn.download(np.uint8, (nr // 8 * nd,)).tobytes(),
                     dk.download(np.uint32, (nd,)).tolist(), dst.download(np.uint32, (4,)).tolist(), n_dets,
                     dd.download(np.uint8, (n_dets * 16,)).tobytes(), dm.download(np.uint8, (nr * nd * 4,)).tobytes())
-        g, exe = hip.capture(s, calls)
         try:
-            fresh()
-            calls()
-            hip.ok(hip.lib.hipStreamSynchronize(s))
-            direct = result()
-            want = R.excise(dirty, R.INTERP)
-            assert direct[0] == want[0].tobytes() and direct[1] == R.mask_words(want[1]).tobytes()
-            assert direct[2] == want[2].ravel().tolist() and direct[3] == want[3].tolist() and 0 < direct[4] <= cap
-            for _ in range(2):
+            with hip.graph(calls) as (exe, s):
                 fresh()
-                hip.replay(exe, s)
-                assert result() == direct
+                calls(s)
+                hip.ok(hip.lib.hipStreamSynchronize(s))
+                direct = result()
+                want = R.excise(dirty, R.INTERP)
+                assert direct[0] == want[0].tobytes() and direct[1] == R.mask_words(want[1]).tobytes()
+                assert direct[2] == want[2].ravel().tolist() and direct[3] == want[3].tolist() and 0 < direct[4] <= cap
+                for _ in range(2):
+                    fresh()
+                    hip.replay(exe, s)
+                    assert result() == direct
         finally:
-            hip.lib.hipGraphExecDestroy(exe)
-            hip.lib.hipGraphDestroy(g)
-            hip.lib.hipStreamDestroy(s)
             for b in (dc, dm, dk, dn, dd, ds, dst):
                 b.free()

@@ -34,7 +34,7 @@ import fmcw_oracle as O
 import kernel_matrix as K
 from conftest import rel_err
 from fmcw import DET_DTYPE, DeviceBuffer, RadarCore
-from test_gpu_parity import check_map, run_cfar_stage, run_range_ct
+from gpu_support import check_map, run_cfar_stage, run_range_ct
 
 pytestmark = pytest.mark.gpu
 

@@ -20,16 +20,12 @@ from fmcw import (DET_DTYPE, MPLOT_DTYPE, PLOT_DTYPE, BeamFormer, BeamMerger, Be
                   DeviceTwsTracker, PlotExtractor, RadarCore, steering_weights, synth)
 from beams_ref import assert_maps_match, beams_ref
 from bearings_ref import assert_bearings_match, bearings_ref
-from merge_ref import HAND, assert_mplots_match, hand_records, merge_ref
+from gpu_support import SENTINEL, Hip, run_rec_list
+from merge_ref import HAND, assert_mplots_match, hand_records, merge_ref, random_list, tile_edge_list
 from plots_ref import assert_plots_match, plots_ref
-from test_gpu_r05 import _Hip
-from test_merge_host import random_list, tile_edge_list
 from tile_edge import TILE_EDGE_SIZES
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = 0xA5
-GUARD = 0xA5A5A5A5
 
 
 def as_plots(p):
@@ -46,30 +42,11 @@ def plots_per_map(dets, nr, nd, win=(1, 1)):
 
 def run(mg, recs, n_maps, out_cap=None, rec_cap=None, n_word=None):
     """One fmcw_merge_enqueue on a host list: (status words, merged plots written, the sentinel-filled
-    output buffer's bytes after them).  The status words sit between two guard words."""
-    n, stride = len(recs), recs.dtype.itemsize
-    rec_cap = n if rec_cap is None else rec_cap
-    out_cap = max(n, 1) if out_cap is None else out_cap
-    dr = DeviceBuffer(max(n, 1) * stride)
-    if n:
-        dr.upload(np.ascontiguousarray(recs))
-    dn = DeviceBuffer(16)
-    dn.upload(np.array([n if n_word is None else n_word, 0, 0, 0], np.uint32))
-    slots = out_cap + 4
-    do = DeviceBuffer(slots * 32)
-    do.upload(np.full(slots * 32, SENTINEL, np.uint8))
-    ds = DeviceBuffer(32)
-    ds.upload(np.full(8, GUARD, np.uint32))
-    try:
-        mg.enqueue(dr, stride, rec_cap, dn, n_maps, do, out_cap, ds.ptr + 16)
-        st = ds.download(np.uint32, (8,))
-        raw = do.download(np.uint8, (slots * 32,))
-    finally:
-        for b in (dr, dn, do, ds):
-            b.free()
-    assert np.all(st[:4] == GUARD) and st[7] == GUARD, "words around the status words were written"
-    k = min(int(st[4]), out_cap)
-    return st[4:7], raw[: k * 32].view(MPLOT_DTYPE).copy(), raw[k * 32:]
+    output buffer's bytes after them).  The status words sit between four guard words and one."""
+    def enqueue(dr, stride, rec_cap, dn, do, out_cap, ds):
+        mg.enqueue(dr, stride, rec_cap, dn, n_maps, do, out_cap, ds)
+    out_cap = max(len(recs), 1) if out_cap is None else out_cap
+    return run_rec_list(enqueue, recs, MPLOT_DTYPE, 3, out_cap, rec_cap, n_word, guards=(4, 1))
 
 
 def check(recs, nr, nd, nb, win, wrap=False, n_maps=None, grids=(0,), **kw):
@@ -304,7 +281,7 @@ def test_graph_capture_cfar_plots_merge(gpu):
             m[s * nb + b + 1, r, d] += 30.0
         return m
     inputs = [maps_of(41), maps_of(42)]
-    hip = _Hip()
+    hip = Hip()
     cap = n_maps * nr * nd
     with RadarCore(N_RANGE=nr, N_DOPPLER=nd, cfar="os1d", max_frames=n_maps) as core, \
             PlotExtractor(nr, nd, win=(1, 1), max_dets=cap) as px, \
@@ -313,36 +290,32 @@ def test_graph_capture_cfar_plots_merge(gpu):
         dd, dn = DeviceBuffer(cap * 16), DeviceBuffer(16)
         dp, dps = DeviceBuffer(cap * 32), DeviceBuffer(8)
         do, dst = DeviceBuffer(cap * 32), DeviceBuffer(12)
-        s = hip.stream()
 
-        def chain():
+        def chain(s):
             core.cfar(dm, n_maps, dd, cap, dn, stream=s.value)
             px.enqueue(dd, cap, dn, dp, cap, dps, stream=s.value)
             mg.enqueue(dp, 32, cap, dps, n_maps, do, cap, dst, stream=s.value)
-        g, exe = hip.capture(s, chain)
         try:
-            seen = []
-            for k in (0, 1, 0):
-                dm.upload(inputs[k])
-                hip.replay(exe, s)
-                n = int(dn.download(np.uint32, (4,))[0])
-                dets = dd.download(DET_DTYPE, (n,))
-                want_p = plots_ref(dets, nr, nd, 1, 1)
-                ps = dps.download(np.uint32, (2,))
-                assert n > 0 and list(ps) == [len(want_p), 0], (k, n, ps)
-                plots = dp.download(PLOT_DTYPE, (len(want_p),))
-                assert_plots_match(plots, want_p)
-                want_m, _ = merge_ref(plots, nr, nd, nb, (1, 1, 1), n_maps=n_maps)
-                st = dst.download(np.uint32, (3,))
-                assert list(st) == [len(want_m), 0, 0] and 0 < len(want_m) < len(plots), (k, st)
-                got = do.download(MPLOT_DTYPE, (len(want_m),))
-                assert_mplots_match(got, want_m, (1, 1, 1))
-                seen.append(got.tobytes())
-            assert seen[0] == seen[2] and seen[0] != seen[1]   # the replays saw their own maps
+            with hip.graph(chain) as (exe, s):
+                seen = []
+                for k in (0, 1, 0):
+                    dm.upload(inputs[k])
+                    hip.replay(exe, s)
+                    n = int(dn.download(np.uint32, (4,))[0])
+                    dets = dd.download(DET_DTYPE, (n,))
+                    want_p = plots_ref(dets, nr, nd, 1, 1)
+                    ps = dps.download(np.uint32, (2,))
+                    assert n > 0 and list(ps) == [len(want_p), 0], (k, n, ps)
+                    plots = dp.download(PLOT_DTYPE, (len(want_p),))
+                    assert_plots_match(plots, want_p)
+                    want_m, _ = merge_ref(plots, nr, nd, nb, (1, 1, 1), n_maps=n_maps)
+                    st = dst.download(np.uint32, (3,))
+                    assert list(st) == [len(want_m), 0, 0] and 0 < len(want_m) < len(plots), (k, st)
+                    got = do.download(MPLOT_DTYPE, (len(want_m),))
+                    assert_mplots_match(got, want_m, (1, 1, 1))
+                    seen.append(got.tobytes())
+                assert seen[0] == seen[2] and seen[0] != seen[1]   # the replays saw their own maps
         finally:
-            hip.lib.hipGraphExecDestroy(exe)
-            hip.lib.hipGraphDestroy(g)
-            hip.lib.hipStreamDestroy(s)
             for b in (dm, dd, dn, dp, dps, do, dst):
                 b.free()
 

@@ -8,7 +8,6 @@ Tolerances (BASELINE.json north_star; SURVEY.md 7 "Hard parts"):
     lists agree except cells whose |cut - threshold| / threshold < 1e-4 (decided by fp32
     rounding of the FFT, not by the CFAR).
 """
-import ctypes as C
 import json
 
 import numpy as np
@@ -16,59 +15,10 @@ import pytest
 
 import fmcw_oracle as O
 from conftest import GOLDEN, rel_err
-from fmcw import RadarCore, DeviceBuffer, DET_DTYPE, magnitude, synth
+from fmcw import RadarCore, DeviceBuffer, magnitude, synth
+from gpu_support import MAP_TOL, check_map, oracle_dets, run_cfar_stage, run_range_ct, to_complex
 
 pytestmark = pytest.mark.gpu
-
-MAP_TOL = 1e-4
-
-
-def check_map(gpu, ref, tol=MAP_TOL):
-    for f in range(ref.shape[0]):
-        e = rel_err(gpu[f], ref[f])
-        assert e <= tol, f"frame {f}: max rel err {e:.3g}"
-        big = np.abs(ref[f]) >= 1e-3 * np.abs(ref[f]).max()
-        pb = np.max(np.abs(gpu[f][big] - ref[f][big]) / np.abs(ref[f][big]))
-        assert pb <= tol, f"frame {f}: per-bin rel err {pb:.3g}"
-
-
-def to_complex(cube, dtype):
-    if dtype == "f32":
-        return cube.astype(np.complex128)
-    x = cube.astype(np.float64)
-    return x[..., 0] + 1j * x[..., 1]
-
-
-def run_range_ct(core, cube, nf):
-    c = core.cfg
-    din = DeviceBuffer(cube.nbytes)
-    din.upload(cube)
-    spec = DeviceBuffer(nf * c.n_rx * c.n_range * c.n_doppler * 8)
-    core.range_ct(din, spec, nf)
-    return spec.download(np.complex64, (nf, c.n_rx, c.n_range, c.n_doppler))
-
-
-def run_cfar_stage(core, mag, cap=1 << 16):
-    nf = mag.shape[0]
-    dm = DeviceBuffer(mag.nbytes)
-    dm.upload(np.ascontiguousarray(mag, np.float32))
-    dd = DeviceBuffer(cap * 16)
-    dn = DeviceBuffer(16)
-    core.cfar(dm, nf, dd, cap, dn)
-    n, dropped = (int(x) for x in dn.download(np.uint32, (2,)))
-    assert n <= cap and dropped == 0
-    return dd.download(DET_DTYPE, (cap,))[:n]
-
-
-def oracle_dets(mag32, cfar):
-    out = []
-    for f in range(mag32.shape[0]):
-        if isinstance(cfar, O.Cfar1D):
-            det, thr = O.cfar_os1d(mag32[f], cfar)
-        else:
-            det, thr = O.cfar_os2d(mag32[f], cfar)
-        out.append(O.detections(det, mag32[f], thr, frame=f))
-    return np.concatenate(out) if out else np.empty(0, O.DET_DTYPE)
 
 
 # ------------------------------------------------------------------------------------------

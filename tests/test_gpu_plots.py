@@ -7,22 +7,18 @@ order and the count exact; sum_mag within 1e-5 relative (<= 81 positive fp32 ter
 plus 4 * 4.8e-6 for the division, about 4e-5).
 """
 import functools
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import reclist_cases as RC
-from conftest import GOLDEN, PKG
+from conftest import GOLDEN
 from fmcw import (RadarCore, BeamMerger, DeviceBuffer, DET_DTYPE, PLOT_DTYPE, PlotExtractor, TwsTracker, formats,
                   synth)
 from plots_ref import plots_ref, assert_plots_match
-from test_gpu_r05 import _Hip
+from gpu_support import SENTINEL, Hip, cli, run_rec_list
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = 0xA5
 
 
 def mk(rows):
@@ -45,27 +41,11 @@ def random_list(seed, nf, nr, nd, density, levels=5):
 
 def run(px, dets, plot_cap=None, det_cap=None, n_word=None):
     """One fmcw_plots_enqueue on a host list: (status words, plots written, the sentinel-filled plot
-    buffer's bytes after them)."""
-    n = len(dets)
-    det_cap = n if det_cap is None else det_cap
-    plot_cap = max(n, 1) if plot_cap is None else plot_cap
-    dd = DeviceBuffer(max(n, 1) * 16)
-    if n:
-        dd.upload(dets)
-    dn = DeviceBuffer(16)
-    dn.upload(np.array([n if n_word is None else n_word, 0, 0, 0], np.uint32))
-    slots = plot_cap + 4
-    dp = DeviceBuffer(slots * 32)
-    dp.upload(np.full(slots * 32, SENTINEL, np.uint8))
-    ds = DeviceBuffer(8)
-    ds.upload(np.array([0xDEAD, 0xBEEF], np.uint32))
-    px.enqueue(dd, det_cap, dn, dp, plot_cap, ds)
-    st = ds.download(np.uint32, (2,))
-    raw = dp.download(np.uint8, (slots * 32,))
-    k = min(int(st[0]), plot_cap)
-    for b in (dd, dn, dp, ds):
-        b.free()
-    return st, raw[: k * 32].view(PLOT_DTYPE).copy(), raw[k * 32:]
+    buffer's bytes after them).  The two status words sit between guard words."""
+    def enqueue(dd, stride, det_cap, dn, dp, plot_cap, ds):
+        px.enqueue(dd, det_cap, dn, dp, plot_cap, ds)
+    plot_cap = max(len(dets), 1) if plot_cap is None else plot_cap
+    return run_rec_list(enqueue, dets, PLOT_DTYPE, 2, plot_cap, det_cap, n_word, guards=(4, 2))
 
 
 def check(dets, nr, nd, win, **kw):
@@ -311,20 +291,18 @@ def test_graph_capture_after_enqueue(gpu):
     ns, nc, nf = 256, 64, 2
     cubes = [np.ascontiguousarray(synth.frames(nf, ns, nc, 1, "two_targets", seed=71)),
              np.ascontiguousarray(synth.frames(nf, ns, nc, 1, "random_target", seed=72))]
-    hip = _Hip()
+    hip = Hip()
     cap, pcap = nf * ns * nc, 4096
     with RadarCore(N_RANGE=ns, N_DOPPLER=nc, cfar="os2d", max_frames=nf) as core, \
             PlotExtractor(ns, nc, win=(1, 1), max_dets=cap) as px:
         dc = DeviceBuffer(cubes[0].nbytes)
         dd, dn = DeviceBuffer(cap * 16), DeviceBuffer(16)
         dp, ds = DeviceBuffer(pcap * 32), DeviceBuffer(8)
-        s = hip.stream()
 
-        def both():
+        def both(s):
             core.enqueue(dc, nf, None, dd, cap, dn, stream=s.value)
             px.enqueue(dd, cap, dn, dp, pcap, ds, stream=s.value)
-        g, exe = hip.capture(s, both)
-        try:
+        with hip.graph(both) as (exe, s):
             counts = []
             for k in (0, 1, 0):
                 dc.upload(cubes[k])
@@ -337,10 +315,6 @@ def test_graph_capture_after_enqueue(gpu):
                 assert_plots_match(dp.download(PLOT_DTYPE, (len(want),)), want)
                 counts.append(dets.tobytes())
             assert counts[0] == counts[2] and counts[0] != counts[1]   # the replays saw their own cubes
-        finally:
-            hip.lib.hipGraphExecDestroy(exe)
-            hip.lib.hipGraphDestroy(g)
-            hip.lib.hipStreamDestroy(s)
 
 
 def _firm_near(tracks, r, d, nd, gate_r=10, gate_d=5):
@@ -375,19 +349,14 @@ def test_end_to_end_tracker(gpu):
     assert len(firm["plots"]) >= 1 and len(firm["dets"]) == 0, firm
 
 
-def _cli(*args):
-    return subprocess.run([sys.executable, "-m", "fmcw.cli", *map(str, args)], cwd=str(PKG),
-                          capture_output=True, text=True, timeout=300, check=True)
-
-
 def test_cli_plots(gpu, tmp_path):
     """--plots --tracks on the golden chirp writes ADR_plots.txt (the reference on the run's own
     detections); without --plots the files are the same as before (no ADR_plots.txt, the same
     detection and track files)."""
     common = (GOLDEN / "golden_input_chirp.txt", "--n-range", 256, "--n-doppler", 128, "--cfar", "os1d", "--tracks")
     a, b = tmp_path / "plain", tmp_path / "plots"
-    _cli(*common, "--out-dir", a)
-    _cli(*common, "--out-dir", b, "--plots", "--plot-window", 1, 2)
+    cli(*common, "--out-dir", a)
+    cli(*common, "--out-dir", b, "--plots", "--plot-window", 1, 2)
     assert sorted(p.name for p in a.iterdir()) == ["ADR_detections.txt", "ADR_tracks.txt"]
     assert sorted(p.name for p in b.iterdir()) == ["ADR_detections.txt", "ADR_plots.txt", "ADR_tracks.txt"]
     assert (a / "ADR_detections.txt").read_bytes() == (b / "ADR_detections.txt").read_bytes()

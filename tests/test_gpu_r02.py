@@ -13,18 +13,15 @@ bin above 1e-3 of the peak; detections bit-exact against the oracle CFAR on the 
 (checked with oracle/fmcw_cpu.c where the NumPy oracle would need GBs: that C CFAR is itself
 pinned bit-exact to the oracle by tests/test_cpu_backend.py).
 """
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import cpu_backend as CB
 import fmcw_oracle as O
-from conftest import GOLDEN, PKG, rel_err
+from conftest import GOLDEN, rel_err
 from fmcw import DET_DTYPE, DeviceBuffer, RadarCore, formats, synth
 from fmcw.dist import RcclGather
-from test_gpu_parity import check_map, oracle_dets, run_cfar_stage, run_range_ct, to_complex
+from gpu_support import check_map, cli, oracle_dets, rtl_dets, run_cfar_stage, run_range_ct, to_complex
 
 pytestmark = pytest.mark.gpu
 
@@ -194,17 +191,6 @@ def test_negative_and_negative_zero_cells(kind):
     assert (40, 10) in set(zip(got["range"].tolist(), got["doppler"].tolist()))
 
 
-def _rtl_dets(maps, cf):
-    out = []
-    for f in range(maps.shape[0]):
-        if isinstance(cf, O.Cfar1D):
-            det, thr = O.cfar_os1d_rtl(maps[f], cf)
-        else:
-            det, thr = O.cfar_os2d_rtl(maps[f], cf)
-        out.append(O.detections_rtl(det, maps[f], thr, frame=f))
-    return np.concatenate(out)
-
-
 @pytest.mark.parametrize("kind", ["os1d", "os2d"])
 def test_compat_cfar_stage(kind):
     """FMCW_COMPAT_CFAR through fmcw_cfar on maps whose cells span the 17-bit range (so the 1-D
@@ -225,7 +211,7 @@ def test_compat_cfar_stage(kind):
     cf = O.Cfar1D() if kind == "os1d" else O.Cfar2D()
     with RadarCore(N_RANGE=128, N_DOPPLER=128, cfar=kind, compat_rtl=("cfar",), max_frames=2) as core:
         got = run_cfar_stage(core, m)
-    want = _rtl_dets(m, cf)
+    want = rtl_dets(m, cf)
     assert len(want) > 0
     np.testing.assert_array_equal(got, want)
 
@@ -239,7 +225,7 @@ def test_compat_cfar_tb_map():
     with RadarCore(N_RANGE=64, N_DOPPLER=32, CFAR_REF_R=rd, CFAR_GUARD_R=gd, CFAR_REF_D=rr,
                    CFAR_GUARD_D=gr, cfar="os2d", compat_rtl=("cfar",)) as core:
         got = run_cfar_stage(core, z["map"].astype(np.float32)[None])
-    np.testing.assert_array_equal(got, _rtl_dets(z["map"].astype(np.float32)[None], p))
+    np.testing.assert_array_equal(got, rtl_dets(z["map"].astype(np.float32)[None], p))
     pos = set(zip(got["range"].tolist(), got["doppler"].tolist()))
     assert (30, 16) in pos and (50, 8) in pos
 
@@ -253,7 +239,7 @@ def test_compat_cfar_fused_1d():
                    compat_rtl=("cfar",), range_shift=10, max_frames=2) as core:
         out = core.process(cube)
         exact = run_cfar_stage(core, out.rd_map)
-    want = _rtl_dets(out.rd_map, O.Cfar1D())
+    want = rtl_dets(out.rd_map, O.Cfar1D())
     np.testing.assert_array_equal(out.dets, want)
     np.testing.assert_array_equal(exact, want)
     assert (out.rd_map < 131072).mean() > 0.99       # the map lives in the 17-bit word range
@@ -327,16 +313,11 @@ def test_rccl_gather_one_rank():
         g.close()
 
 
-def _cli(*args):
-    return subprocess.run([sys.executable, "-m", "fmcw.cli", *map(str, args)], cwd=str(PKG),
-                          capture_output=True, text=True, timeout=300, check=True)
-
-
 def test_cli_golden_chirp_writes_visualizer_files(tmp_path):
     """python -m fmcw.cli on data/golden_input_chirp.txt (config-1 framing): the detection file
     parses under the visualizer's rule (3 integer tokens) and equals RadarCore's own list; the
     map file is data/radar_output.txt's 5-column format; --doppler-centred shifts by N/2."""
-    _cli(GOLDEN / "golden_input_chirp.txt", "--n-range", 256, "--n-doppler", 128, "--cfar", "os1d",
+    cli(GOLDEN / "golden_input_chirp.txt", "--n-range", 256, "--n-doppler", 128, "--cfar", "os1d",
          "--out-dir", tmp_path, "--map-file", "radar_output.txt")
     iq = formats.read_adc_pairs(GOLDEN / "golden_input_chirp.txt")
     with RadarCore(N_RANGE=256, N_DOPPLER=128, cfar="os1d") as core:
@@ -348,7 +329,7 @@ def test_cli_golden_chirp_writes_visualizer_files(tmp_path):
     np.testing.assert_array_equal(m, np.rint(out.rd_map[0].astype(np.float64)).astype(np.int64))
     assert np.unravel_index(np.argmax(m), m.shape) == (73, 0)
     cdir = tmp_path / "centred"
-    _cli(GOLDEN / "golden_input_chirp.txt", "--n-range", 256, "--n-doppler", 128, "--cfar", "os1d",
+    cli(GOLDEN / "golden_input_chirp.txt", "--n-range", 256, "--n-doppler", 128, "--cfar", "os1d",
          "--out-dir", cdir, "--map-file", "radar_output.txt", "--doppler-centred")
     mc = formats.read_rd_map(cdir / "radar_output.txt", 256, 128)
     assert np.unravel_index(np.argmax(mc), mc.shape) == (73, 64)      # zero Doppler at N/2
@@ -364,7 +345,7 @@ def test_cli_axi_bin_stream(tmp_path):
     words = pack_adc_words(cpis[..., 0].reshape(-1), cpis[..., 1].reshape(-1)).astype("<u4")
     b = tmp_path / "stream.bin"
     words.tofile(b)
-    _cli(b, "--n-range", 1024, "--n-doppler", 128, "--cfar", "os1d", "--out-dir", tmp_path)
+    cli(b, "--n-range", 1024, "--n-doppler", 128, "--cfar", "os1d", "--out-dir", tmp_path)
     with RadarCore(N_RANGE=1024, N_DOPPLER=128, in_dtype="i16", cfar="os1d", max_frames=2) as core:
         out = core.process(np.ascontiguousarray(cpis[:, None]))
     got = formats.read_detections(tmp_path / "ADR_detections.txt")

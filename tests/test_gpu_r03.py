@@ -16,7 +16,7 @@ import fmcw_oracle as O
 from conftest import rel_err
 from fmcw import RadarCore, DeviceBuffer, DET_DTYPE, synth
 from fmcw import _lib as L
-from test_gpu_parity import check_map, oracle_dets, run_range_ct, to_complex
+from gpu_support import check_map, oracle_dets, run_range_ct, to_complex
 
 pytestmark = pytest.mark.gpu
 

@@ -17,7 +17,7 @@ import cpu_backend as CB
 import fmcw_oracle as O
 from conftest import REPO
 from fmcw import RadarCore, synth
-from test_gpu_parity import check_map, run_cfar_stage, to_complex
+from gpu_support import check_map, run_cfar_stage, to_complex
 
 pytestmark = pytest.mark.gpu
 

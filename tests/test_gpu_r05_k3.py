@@ -12,8 +12,7 @@ import pytest
 import cpu_backend as CB
 import fmcw_oracle as O
 from fmcw import RadarCore
-from test_gpu_parity import run_cfar_stage
-from test_gpu_r02 import _rtl_dets
+from gpu_support import rtl_dets, run_cfar_stage
 
 pytestmark = pytest.mark.gpu
 
@@ -82,7 +81,7 @@ def test_lv_compat():
     m[1, 50, 50] = -5.0
     with RadarCore(N_RANGE=NS, N_DOPPLER=NC, cfar="os2d", compat_rtl=("cfar",), max_frames=2) as core:
         got = run_cfar_stage(core, m, cap=1 << 20)
-    want = _rtl_dets(m, O.Cfar2D())
+    want = rtl_dets(m, O.Cfar2D())
     assert len(want) > 0
     np.testing.assert_array_equal(got, want)
 

@@ -19,13 +19,9 @@ import cpu_backend as CB
 import fmcw_oracle as O
 from fmcw import RadarCore, DeviceBuffer, DET_DTYPE, synth
 from fmcw import _lib as L
-from test_gpu_r05 import _Hip
+from gpu_support import Hip, check_map, rayleigh
 
 pytestmark = pytest.mark.gpu
-
-
-def _rayleigh(seed, nf, ns, nc):
-    return np.random.default_rng(seed).rayleigh(1.0, (nf, ns, nc)).astype(np.float32)
 
 
 def _run_cfar(core, maps, cap):
@@ -44,7 +40,7 @@ def test_dense_os2d_scale_override_1():
     """2-D OS-CFAR with the reference's cfar_scale_ovr = 1 on 2 x 1024 x 256 Rayleigh maps:
     ~27 % of the cells detect (the scratch of round 5 held 4.7 %); every record bit-exact."""
     ns, nc, nf = 1024, 256, 2
-    maps = _rayleigh(61, nf, ns, nc)
+    maps = rayleigh(nf, ns, nc, 61)
     want = CB.cfar(maps, O.Cfar2D(scale_override=1), threads=16, cap=1 << 22)
     assert len(want) > 0.15 * maps.size
     with RadarCore(N_RANGE=ns, N_DOPPLER=nc, cfar="os2d", cfar_scale_ovr=1, max_frames=nf) as core:
@@ -56,7 +52,7 @@ def test_dense_os2d_scale_override_1():
 def test_dense_os1d_alpha_1():
     """1-D OS-CFAR 16/4 with alpha = 1 on Rayleigh maps (~24 % detect) through fmcw_cfar."""
     ns, nc, nf = 1024, 256, 3
-    maps = _rayleigh(62, nf, ns, nc)
+    maps = rayleigh(nf, ns, nc, 62)
     cf = O.Cfar1D(alpha=1.0)
     want = CB.cfar(maps, cf, threads=16, cap=1 << 22)
     assert len(want) > 0.15 * maps.size
@@ -97,25 +93,19 @@ def test_graph_capture_lattice_3():
     maps = [dense, sparse]
     want = [CB.cfar(m, O.Cfar2D(), threads=16, cap=1 << 22) for m in maps]
     assert len(want[0]) > 80000
-    hip = _Hip()
+    hip = Hip()
     with RadarCore(N_RANGE=ns, N_DOPPLER=nc, cfar="os2d", max_frames=nf) as core:
         dm = DeviceBuffer(dense.nbytes)
         cap = 1 << 20
         dd = DeviceBuffer(cap * 16)
         dn = DeviceBuffer(16)
-        s = hip.stream()
-        g, exe = hip.capture(s, lambda: core.cfar(dm, nf, dd, cap, dn, stream=s.value))
-        try:
+        with hip.graph(lambda s: core.cfar(dm, nf, dd, cap, dn, stream=s.value)) as (exe, s):
             for k in (0, 1, 0):
                 dm.upload(maps[k])
                 hip.replay(exe, s)
                 st = dn.download(np.uint32, (4,))
                 assert int(st[0]) == len(want[k]) and st[1] == 0, (k, st)
                 np.testing.assert_array_equal(dd.download(DET_DTYPE, (int(st[0]),)), want[k])
-        finally:
-            hip.lib.hipGraphExecDestroy(exe)
-            hip.lib.hipGraphDestroy(g)
-            hip.lib.hipStreamDestroy(s)
 
 
 def test_det_cap_is_the_only_bound():
@@ -123,7 +113,7 @@ def test_det_cap_is_the_only_bound():
     word 1 = 0 (nothing lost inside the library); fmcw_process returns FMCW_EDETCAP with the
     required count, and a retry with that capacity returns the whole list."""
     ns, nc, nf = 1024, 256, 2
-    maps = _rayleigh(64, nf, ns, nc)
+    maps = rayleigh(nf, ns, nc, 64)
     cf = O.Cfar2D(scale_override=1)
     want = CB.cfar(maps, cf, threads=16, cap=1 << 22)
     short = len(want) // 3
@@ -147,7 +137,7 @@ def test_det_capacity_bounds_the_scratch():
     status word 1 (and a list that is not complete); one with det_capacity >= the count loses
     nothing."""
     ns, nc, nf = 1024, 256, 2
-    maps = _rayleigh(66, nf, ns, nc)
+    maps = rayleigh(nf, ns, nc, 66)
     cf = O.Cfar2D(scale_override=1)
     want = CB.cfar(maps, cf, threads=16, cap=1 << 22)
     with RadarCore(N_RANGE=ns, N_DOPPLER=nc, cfar="os2d", cfar_scale_ovr=1, max_frames=nf,
@@ -215,7 +205,6 @@ def test_s48_adversarial_dynamic_range(case, spectrum):
     detected; detections bit-exact vs the C oracle's 1-D CFAR on the GPU's map.  (f32: the same
     cases on the fp32 spectrum, as a control.)  A NumPy model of the S48 rounding alone
     (round-to-nearest 23-bit significands per strided quad) puts these at <= 4e-5 per bin."""
-    from test_gpu_parity import check_map
     ns, nc, nf = 1024, 256, 2
     cube = _adversarial(case, nf, ns, nc, seed={"interferer": 91, "interferer_wide": 92, "clutter60": 93}[case])
     with RadarCore(N_RANGE=ns, N_DOPPLER=nc, cfar="os1d", max_frames=nf, spectrum=spectrum) as core:

@@ -14,27 +14,15 @@ import pytest
 
 import scenario_ref as S
 from conftest import rel_err
-from fmcw import DET_DTYPE, PLOT_DTYPE, TRACK_DTYPE, DeviceBuffer, PlotExtractor, RadarCore, TwsTracker
+from fmcw import TRACK_DTYPE, TwsTracker
 from plots_ref import assert_plots_match
-from test_gpu_parity import MAP_TOL, check_map, run_cfar_stage, run_range_ct
-from test_gpu_r05 import _Hip
-from test_gpu_tws_dev import RTL, SENTINEL, assert_matches, tracker
+from gpu_support import GUARD, MAP_TOL, RTL, Chain, Hip, assert_matches, check_map, make_core, run_cfar_stage, run_range_ct
 
 pytestmark = pytest.mark.gpu
 
 CASES = [(s, m, p) for s in S.SCENES for m in S.MTI_MODES for p in S.PATHS]
 CASE_IDS = [f"{s.id}-mti{m}-{p}" for s, m, p in CASES]
 KEY = ["range", "doppler", "mag", "threshold"]
-
-
-def make_core(scene, mti, path, max_frames, **over):
-    kw = dict(N_RANGE=scene.ns, N_DOPPLER=scene.nc, in_dtype="i16", cfar="os2d", max_frames=max_frames,
-              mti_bypass=(mti == 0), NOTCH_MODE=mti or 2, **scene.generics)
-    if path == "int":       # FMCW_COMPAT_MTI needs the canceller on; the Q15 window selects the words anyway
-        kw.update(window="q15_rtl", range_shift=S.INT_SHIFT[scene.id, mti],
-                  compat_rtl=("cfar", "mti") if mti else ("cfar",))
-    kw.update(over)
-    return RadarCore(**kw)
 
 
 def same_output(a, b):
@@ -116,98 +104,7 @@ def test_process(gpu, scene, mti, path):
     assert S.facts(scene, out.dets, out.rd_map, path) == S.facts(scene, host.dets, host.maps.astype(np.float32), path)
 
 
-# ---- the device chain ------------------------------------------------------------------------
-GUARD = 64
-
-
-class Guarded:
-    """A device buffer with GUARD sentinel bytes behind its `nbytes`."""
-
-    def __init__(self, nbytes):
-        self.nbytes = nbytes
-        self.buf = DeviceBuffer(nbytes + GUARD)
-        self.fill()
-
-    def fill(self):
-        self.buf.upload(np.full(self.nbytes + GUARD, SENTINEL, np.uint8))
-
-    @property
-    def ptr(self):
-        return self.buf.ptr
-
-    def get(self, dtype, shape):
-        return self.buf.download(dtype, shape)
-
-    def check(self):
-        assert np.all(self.buf.download(np.uint8, (GUARD,), offset=self.nbytes) == SENTINEL)
-
-    def free(self):
-        self.buf.free()
-
-
-class Chain:
-    """fmcw_enqueue (map and detections), fmcw_plots_enqueue, fmcw_tws_dev_enqueue on one stream, every
-    output buffer guarded."""
-
-    def __init__(self, hip, scene, n_frames, n_streams, rtl):
-        self.scene, self.nf, self.ns, self.rtl, self.hip = scene, n_frames, n_streams, rtl, hip
-        self.max_scans = n_frames // n_streams
-        self.cap = 512 * n_frames
-        self.frame_bytes = scene.nc * scene.ns * 4
-        self.core = make_core(scene, 2, "float", n_frames)
-        self.px = PlotExtractor(scene.ns, scene.nc, win=S.PLOT_WIN, max_dets=self.cap)
-        self.trk = tracker(n_streams, self.max_scans, rtl, **S.TWS)
-        self.cube = DeviceBuffer(n_frames * self.frame_bytes)
-        self.map = Guarded(n_frames * scene.ns * scene.nc * 4)
-        self.dets, self.n_dets = Guarded(self.cap * 16), Guarded(16)
-        self.plots, self.n_plots = Guarded(S.PLOT_CAP * 32), Guarded(8)
-        self.tracks = Guarded(n_frames * S.TRACK_CAP * 28)
-        self.counts, self.status = Guarded(n_frames * 8), Guarded(8)
-        self.stream = hip.stream()
-
-    def outputs(self):
-        return (self.map, self.dets, self.n_dets, self.plots, self.n_plots, self.tracks, self.counts, self.status)
-
-    def enqueue(self, first=0, n_frames=None):
-        """The three calls on frames first .. first + n_frames of the uploaded cube."""
-        nf = self.nf if n_frames is None else n_frames
-        s = self.stream.value
-        self.core.enqueue(self.cube.ptr + first * self.frame_bytes, nf, self.map.ptr, self.dets.ptr, self.cap,
-                          self.n_dets.ptr, stream=s)
-        self.px.enqueue(self.dets.ptr, self.cap, self.n_dets.ptr, self.plots.ptr, S.PLOT_CAP, self.n_plots.ptr, stream=s)
-        self.trk.enqueue(self.plots.ptr, 32, S.PLOT_CAP, self.n_plots.ptr, nf // self.ns, self.tracks.ptr, S.TRACK_CAP,
-                         self.counts.ptr, self.status.ptr, stream=s)
-
-    def clear(self):
-        for b in self.outputs():
-            b.fill()
-        self.hip.ok(self.hip.lib.hipStreamSynchronize(None))
-
-    def sync(self):
-        self.hip.ok(self.hip.lib.hipStreamSynchronize(self.stream))
-
-    def result(self, n_frames=None):
-        """Everything the three calls wrote, downloaded after the last of them."""
-        nf = self.nf if n_frames is None else n_frames
-        self.sync()
-        for b in self.outputs():
-            b.check()
-        st = self.n_dets.get(np.uint32, (4,))
-        ps = self.n_plots.get(np.uint32, (2,))
-        assert st[0] <= self.cap and st[1] == 0 and ps[0] <= S.PLOT_CAP and ps[1] == 0, (st, ps)
-        return dict(map=self.map.get(np.float32, (nf, self.scene.ns, self.scene.nc)),
-                    dets=self.dets.get(DET_DTYPE, (int(st[0]),)), plots=self.plots.get(PLOT_DTYPE, (int(ps[0]),)),
-                    counts=self.counts.get(np.uint32, (nf, 2)), raw=self.tracks.get(np.uint8, (nf, S.TRACK_CAP * 28)),
-                    status=self.status.get(np.uint32, (2,)))
-
-    def close(self):
-        self.hip.lib.hipStreamDestroy(self.stream)
-        for x in (self.core, self.px, self.trk):
-            x.close()
-        for b in self.outputs() + (self.cube,):
-            b.free()
-
-
+# ---- the device chain (gpu_support.Chain) ----------------------------------------------------
 def verify(scene, res, n_streams, rtl, oracles=None, hosts=None):
     """One chain result against the references, each on the GPU's own previous stage: detections =
     the oracle's CFAR on the GPU's map, plots = plots_ref on the GPU's detections, tracks = tws_dev_ref
@@ -217,7 +114,7 @@ def verify(scene, res, n_streams, rtl, oracles=None, hosts=None):
     assert_plots_match(res["plots"], S.oracle_plots(scene, res["dets"]))
     groups = len(res["counts"])
     want, status, oracles = S.run_tracks(res["plots"], groups // n_streams, rtl, n_streams, oracles)
-    guard = np.full(2, 0xA5A5A5A5, np.uint32)      # (the counts buffer's own guard is Guarded's)
+    guard = np.full(2, GUARD, np.uint32)           # (the counts buffer's own guard is Guarded's)
     assert_matches((res["status"], res["counts"], res["raw"], guard), want, status, n_streams, S.TRACK_CAP)
     assert status == [0, 0]
     hosts = hosts or [TwsTracker(INIT_HITS=S.TWS["init_hits"], COAST_MAX=S.TWS["coast_max"], rtl_compat=rtl)
@@ -250,11 +147,10 @@ def test_device_chain(gpu, rtl):
     later coasts (fact (d)); 4 + 5 scans in two calls give the same tracks (the track file stays on
     the device); the same holds for a second seed's cubes, and the chain captured into a graph and
     replayed on the second seed's cubes, then on the first's, gives each one's eager bytes."""
-    sc, hip = S.CHAIN_SCENE, _Hip()
+    sc, hip = S.CHAIN_SCENE, Hip()
     n = sc.n_scans
     cubes = [np.ascontiguousarray(S.scene_cubes(sc, seed)[0]) for seed in (None, S.CHAIN_SEED_2)]
     ch = Chain(hip, sc, n, 1, rtl)
-    g = exe = None
     try:
         eager = []
         for cube in cubes:
@@ -283,21 +179,17 @@ def test_device_chain(gpu, rtl):
         assert np.concatenate([a["raw"], b["raw"]]).tobytes() == eager[0]["raw"].tobytes()
         assert np.concatenate([a["map"], b["map"]]).tobytes() == eager[0]["map"].tobytes()
 
-        g, exe = hip.capture(ch.stream, ch.enqueue)
-        for k in (1, 0):
-            ch.cube.upload(cubes[k])
-            ch.trk.reset(stream=ch.stream.value)
-            ch.clear()
-            hip.replay(exe, ch.stream)
-            got = ch.result()
-            assert same_tracks(got, eager[k]), k
-            np.testing.assert_array_equal(got["dets"], eager[k]["dets"])
-            assert got["plots"].tobytes() == eager[k]["plots"].tobytes() and got["map"].tobytes() == eager[k]["map"].tobytes()
+        with hip.graph(lambda s: ch.enqueue(), ch.stream) as (exe, _):
+            for k in (1, 0):
+                ch.cube.upload(cubes[k])
+                ch.trk.reset(stream=ch.stream.value)
+                ch.clear()
+                hip.replay(exe, ch.stream)
+                got = ch.result()
+                assert same_tracks(got, eager[k]), k
+                np.testing.assert_array_equal(got["dets"], eager[k]["dets"])
+                assert got["plots"].tobytes() == eager[k]["plots"].tobytes() and got["map"].tobytes() == eager[k]["map"].tobytes()
     finally:
-        if exe:
-            hip.lib.hipGraphExecDestroy(exe)
-        if g:
-            hip.lib.hipGraphDestroy(g)
         ch.close()
 
 
@@ -306,7 +198,7 @@ def test_two_streams(gpu, rtl):
     """Two seeds as the two streams of one tracker: frame m is scan m // 2 of stream m % 2.  The oracle
     gives no scan without detections, so scan 4 of stream 1 is a zero cube (an empty list: the
     stream's tracks coast).  Each stream's tracks equal that seed's one-stream oracle."""
-    sc, hip = S.CHAIN_SCENE, _Hip()
+    sc, hip = S.CHAIN_SCENE, Hip()
     n = sc.n_scans
     a, b = (np.ascontiguousarray(S.scene_cubes(sc, seed)[0]) for seed in (None, S.CHAIN_SEED_2))
     b = b.copy()

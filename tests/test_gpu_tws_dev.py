@@ -16,17 +16,12 @@ import pytest
 
 import tws_oracle as T
 import tws_dev_ref as R
-from fmcw import (DET_DTYPE, PLOT_DTYPE, TRACK_DTYPE, DeviceBuffer, DeviceTwsTracker, FmcwError, PlotExtractor,
-                  RadarCore, TwsTracker, synth)
-from test_gpu_r05 import _Hip
+from fmcw import DET_DTYPE, PLOT_DTYPE, DeviceBuffer, FmcwError, PlotExtractor, RadarCore, TwsTracker, synth
+from gpu_support import GUARD, RTL, SENTINEL, Hip, assert_matches, sentinel_buffer, tracker
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5
 TILE = 1024
-GENERICS = dict(max_tracks="MAX_TRACKS", coast_max="COAST_MAX", init_hits="INIT_HITS", gate_r="ASSOC_GATE_R",
-                gate_d="ASSOC_GATE_D", alpha_q8="ALPHA_GAIN", beta_q8="BETA_GAIN", max_dets="MAX_DETS")
-RTL = pytest.mark.parametrize("rtl", [False, True])
 
 
 def to_records(streams, dtype=DET_DTYPE, first_scan=0):
@@ -42,11 +37,6 @@ def to_records(streams, dtype=DET_DTYPE, first_scan=0):
     return a
 
 
-def tracker(n_streams, max_scans, rtl, **params):
-    return DeviceTwsTracker(n_streams=n_streams, max_scans=max_scans, rtl_compat=rtl,
-                            **{GENERICS[k]: v for k, v in params.items()})
-
-
 def run_dev(trk, recs, n_scans, track_cap=None, rec_cap=None, n_word=None):
     """One fmcw_tws_dev_enqueue on a host list.  Returns (status words, counts [groups][2], the
     sentinel-filled track buffer's bytes [groups][track_cap x 28], the counts' two guard words)."""
@@ -58,10 +48,8 @@ def run_dev(trk, recs, n_scans, track_cap=None, rec_cap=None, n_word=None):
         dr.upload(recs)
     dn = DeviceBuffer(16)
     dn.upload(np.array([n if n_word is None else n_word, 0, 0, 0], np.uint32))
-    dt = DeviceBuffer(max(groups, 1) * cap * 28)
-    dt.upload(np.full(max(groups, 1) * cap * 28, SENTINEL, np.uint8))
-    dc = DeviceBuffer((2 * groups + 2) * 4)
-    dc.upload(np.full(2 * groups + 2, 0xA5A5A5A5, np.uint32))
+    dt = sentinel_buffer(max(groups, 1) * cap * 28)
+    dc = sentinel_buffer((2 * groups + 2) * 4)
     ds = DeviceBuffer(8)
     ds.upload(np.array([0xDEAD, 0xBEEF], np.uint32))
     try:
@@ -73,21 +61,6 @@ def run_dev(trk, recs, n_scans, track_cap=None, rec_cap=None, n_word=None):
         for b in (dr, dn, dt, dc, ds):
             b.free()
     return st, counts[:2 * groups].reshape(groups, 2), raw, counts[2 * groups:]
-
-
-def assert_matches(got, want, want_status, n_streams, track_cap):
-    st, counts, raw, guard = got
-    assert list(st) == want_status, (list(st), want_status)
-    assert list(guard) == [0xA5A5A5A5] * 2
-    for scan, row in enumerate(want):
-        for s, (tracks, active) in enumerate(row):
-            m = scan * n_streams + s
-            assert (int(counts[m, 0]), int(counts[m, 1])) == (len(tracks), active), (scan, s, counts[m])
-            k = min(len(tracks), track_cap)
-            assert R.tracks_equal(raw[m, :k * 28].view(TRACK_DTYPE), tracks[:k]), (scan, s)
-            assert np.all(raw[m, k * 28:] == SENTINEL), (scan, s)
-    if not want:
-        assert np.all(raw == SENTINEL)
 
 
 def check(streams, rtl, grid=0, track_cap=None, dtype=DET_DTYPE, **params):
@@ -237,7 +210,7 @@ def test_empty_list_and_status_words(gpu, rtl):
     recs = to_records([random_scans(22, n_scans=10), random_scans(23, n_scans=10)])
     with tracker(2, 8, rtl) as trk:
         st, counts, raw, guard = run_dev(trk, recs, 0)
-        assert list(st) == [0, len(recs)] and np.all(raw == SENTINEL) and list(guard) == [0xA5A5A5A5] * 2
+        assert list(st) == [0, len(recs)] and np.all(raw == SENTINEL) and list(guard) == [GUARD] * 2
         # n_scans = 0 left the track files at power-up: the next call is a fresh tracker's
         want, status = R.run_ref(recs, 8, 2, R.make_oracles(2, rtl))
         assert status[1] == int(np.sum(recs["frame"] >= 16)) > 0
@@ -380,7 +353,7 @@ def test_end_to_end_on_the_device(gpu, rtl):
     last active track of a call leaves in the state block) advance on every replay."""
     ns, nc, nf = 256, 64, 4
     cube = np.ascontiguousarray(synth.frames(nf, ns, nc, 1, "two_targets", seed=71))
-    hip = _Hip()
+    hip = Hip()
     cap, pcap, tcap = nf * ns * nc, 4096, 32
     with RadarCore(N_RANGE=ns, N_DOPPLER=nc, cfar="os2d", max_frames=nf) as core, \
             PlotExtractor(ns, nc, win=(1, 1), max_dets=cap) as px, tracker(1, nf, rtl, init_hits=1) as trk:
@@ -405,7 +378,6 @@ def test_end_to_end_on_the_device(gpu, rtl):
             dt.upload(np.full(nf * tcap * 28, SENTINEL, np.uint8))
             hip.ok(hip.lib.hipStreamSynchronize(None))
 
-        g = exe = None
         try:
             eager = []
             for _ in range(2):
@@ -427,17 +399,13 @@ def test_end_to_end_on_the_device(gpu, rtl):
                 assert np.frombuffer(eager[0][0], np.uint32).reshape(nf, 2)[-1, 0] >= 1    # a firm track
                 assert eager[0][0] != eager[1][0] or eager[0][1].tobytes() != eager[1][1].tobytes()
             trk.reset(stream=s.value)
-            g, exe = hip.capture(s, chain)
-            for k in range(2):
-                clear()
-                hip.replay(exe, s)
-                got = result()
-                assert got[0] == eager[k][0] and got[1].tobytes() == eager[k][1].tobytes() and got[2] == [0, 0], k
+            with hip.graph(lambda s: chain(), s) as (exe, _):
+                for k in range(2):
+                    clear()
+                    hip.replay(exe, s)
+                    got = result()
+                    assert got[0] == eager[k][0] and got[1].tobytes() == eager[k][1].tobytes() and got[2] == [0, 0], k
         finally:
-            if exe:
-                hip.lib.hipGraphExecDestroy(exe)
-            if g:
-                hip.lib.hipGraphDestroy(g)
             hip.lib.hipStreamDestroy(s)
             for b in (dc, dd, dn, dp, dps, dt, dcnt, dst):
                 b.free()

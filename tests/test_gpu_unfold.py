@@ -16,15 +16,13 @@ import scenario_ref as S
 import tws_dev_ref as TR
 from fmcw import DET_DTYPE, PLOT_DTYPE, TRACK_DTYPE, VPLOT_DTYPE, DeviceBuffer, DeviceTwsTracker, PlotExtractor, VelocityUnfolder
 from plots_ref import assert_plots_match, plots_ref
-from test_gpu_r05 import _Hip
-from test_unfold_host import FIGHTER_FACT, TILE_EDGE_CFG, fighter_fact, scenario_cfg, tile_edge_list
+from gpu_support import SENTINEL, Chain, Hip, run_rec_list
 from tile_edge import TILE_EDGE_SIZES
-from unfold_ref import Cfg, assert_vplots_equal, n_dwells, random_list, unfold_ref
+from unfold_ref import (FIGHTER_FACT, TILE_EDGE_CFG, Cfg, assert_vplots_equal, fighter_fact, n_dwells, random_list, scenario_cfg,
+                        tile_edge_list, unfold_ref)
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5
-GUARD = 0xA5A5A5A5
 NR, NC, SCANS = 64, 32, 9
 UNITS = {2: (8, 9), 3: (8, 9, 10), 4: (7, 8, 9, 11), 5: (7, 8, 9, 11, 13), 8: (7, 8, 9, 11, 13, 15, 16, 17)}
 
@@ -37,30 +35,11 @@ def unfolder(cfg: Cfg, max_recs, max_frames=None):
 
 def run(uf, recs, n_scans, out_cap=None, rec_cap=None, n_word=None, K=4):
     """One fmcw_unfold_enqueue on a host list: (status words, reports written, the sentinel-filled
-    output buffer's bytes after them).  The status words sit between guard words."""
-    n, stride = len(recs), recs.dtype.itemsize
-    rec_cap = n if rec_cap is None else rec_cap
-    out_cap = max(K * n, 1) if out_cap is None else out_cap   # a record reports in at most K dwells
-    dr = DeviceBuffer(max(n, 1) * stride)
-    if n:
-        dr.upload(np.ascontiguousarray(recs))
-    dn = DeviceBuffer(16)
-    dn.upload(np.array([n if n_word is None else n_word, 0, 0, 0], np.uint32))
-    slots = out_cap + 4
-    do = DeviceBuffer(slots * 32)
-    do.upload(np.full(slots * 32, SENTINEL, np.uint8))
-    ds = DeviceBuffer(48)
-    ds.upload(np.full(12, GUARD, np.uint32))
-    try:
-        uf.enqueue(dr, stride, rec_cap, dn, n_scans, do, out_cap, ds.ptr + 16)
-        st = ds.download(np.uint32, (12,))
-        raw = do.download(np.uint8, (slots * 32,))
-    finally:
-        for b in (dr, dn, do, ds):
-            b.free()
-    assert np.all(st[:4] == GUARD) and np.all(st[8:] == GUARD), "words around the status words were written"
-    k = min(int(st[4]), out_cap)
-    return st[4:8], raw[: k * 32].view(VPLOT_DTYPE).copy(), raw[k * 32:]
+    output buffer's bytes after them).  The status words sit between guard words, four on each side."""
+    def enqueue(dr, stride, rec_cap, dn, do, out_cap, ds):
+        uf.enqueue(dr, stride, rec_cap, dn, n_scans, do, out_cap, ds)
+    out_cap = max(K * len(recs), 1) if out_cap is None else out_cap   # a record reports in at most K dwells
+    return run_rec_list(enqueue, recs, VPLOT_DTYPE, 4, out_cap, rec_cap, n_word, guards=(4, 4))
 
 
 def check(recs, n_scans, cfg, grids=(0,), max_recs=None, **kw):
@@ -256,7 +235,7 @@ def test_graph_capture_plots_unfold_tracker(gpu):
     cfg = Cfg(n_range=NR, n_doppler=NC, v_max=3 * NC * 8, step=1)
     dets = random_list(8, SCANS, NR, NC, 280, DET_DTYPE, cfg=cfg)
     nd, cap, tcap = n_dwells(SCANS, 3, 1), 1024, 32
-    hip = _Hip()
+    hip = Hip()
     with PlotExtractor(NR, NC, win=(1, 1), max_dets=cap) as px, unfolder(cfg, cap) as uf, \
             DeviceTwsTracker(n_streams=1, max_scans=nd) as trk:
         dd, dn = DeviceBuffer(cap * 16), DeviceBuffer(16)
@@ -277,7 +256,6 @@ def test_graph_capture_plots_unfold_tracker(gpu):
             ps, vs = dps.download(np.uint32, (2,)), dvs.download(np.uint32, (4,))
             plots = dp.download(PLOT_DTYPE, (int(ps[0]),))
             return plots, vs, dv.download(VPLOT_DTYPE, (int(vs[0]),)), tracks_of(dt, dc, nd, tcap), dts.download(np.uint32, (2,))
-        g = exe = None
         try:
             chain()
             plots, vs, vplots, tracks, ts = result()
@@ -294,32 +272,27 @@ def test_graph_capture_plots_unfold_tracker(gpu):
                 return all(TR.tracks_equal(got[m][0], ref[m][0][0]) and got[m][1] == ref[m][0][1] for m in range(nd))
             assert list(ts) == [0, 0] and same(tracks, ref1) and max(len(t[0]) for t in tracks) > 0
             trk.reset(stream=s.value)
-            g, exe = hip.capture(s, chain)
-            for ref in (ref1, ref2):
-                for b in (dp, dv):
-                    b.upload(np.full(b.nbytes, SENTINEL, np.uint8))
-                hip.replay(exe, s)
-                plots_r, vs_r, vplots_r, tracks_r, ts_r = result()
-                assert plots_r.tobytes() == plots.tobytes() and list(vs_r) == list(vs)
-                assert vplots_r.tobytes() == vplots.tobytes()
-                assert list(ts_r) == [0, 0] and same(tracks_r, ref)
-            assert not same(tracks_r, ref1)                      # the second replay did advance
+            with hip.graph(lambda s: chain(), s) as (exe, _):
+                for ref in (ref1, ref2):
+                    for b in (dp, dv):
+                        b.upload(np.full(b.nbytes, SENTINEL, np.uint8))
+                    hip.replay(exe, s)
+                    plots_r, vs_r, vplots_r, tracks_r, ts_r = result()
+                    assert plots_r.tobytes() == plots.tobytes() and list(vs_r) == list(vs)
+                    assert vplots_r.tobytes() == vplots.tobytes()
+                    assert list(ts_r) == [0, 0] and same(tracks_r, ref)
+                assert not same(tracks_r, ref1)                      # the second replay did advance
         finally:
-            if exe:
-                hip.lib.hipGraphExecDestroy(exe)
-            if g:
-                hip.lib.hipGraphDestroy(g)
             hip.lib.hipStreamDestroy(s)
             for b in (dd, dn, dp, dps, dv, dvs, dt, dc, dts):
                 b.free()
 
 
 def test_scenario_chain(gpu):
-    """CHAIN_SCENE through the GPU chain of test_gpu_scenario (fmcw_enqueue behind the 2-pulse canceller ->
+    """CHAIN_SCENE through gpu_support.Chain (fmcw_enqueue behind the 2-pulse canceller ->
     fmcw_plots_enqueue) to the plot list; the unfolder on that list equals unfold_ref on it, and the
-    fighter fact pinned on the CPU (test_unfold_host.FIGHTER_FACT) holds on it."""
-    from test_gpu_scenario import Chain
-    sc, hip = S.CHAIN_SCENE, _Hip()
+    fighter fact pinned on the CPU (unfold_ref.FIGHTER_FACT) holds on it."""
+    sc, hip = S.CHAIN_SCENE, Hip()
     ch = Chain(hip, sc, sc.n_scans, 1, False)
     try:
         ch.cube.upload(np.ascontiguousarray(S.scene_cubes(sc)[0]))

@@ -14,9 +14,9 @@ from fmcw import DET_DTYPE, MPLOT_DTYPE, PLOT_DTYPE, BeamMerger, steering_weight
 from fmcw import _lib as L
 from fmcw import merge as M
 from beams_ref import beams_ref
-from merge_ref import HAND, hand_records, merge_ref
+from merge_ref import HAND, hand_records, merge_ref, random_list, tile_edge_list
 from plots_ref import plots_ref
-from tile_edge import TILE_EDGE_SIZES, thin_to
+from tile_edge import TILE_EDGE_SIZES
 
 NEW_SYMBOLS = ("fmcw_merge_config_default", "fmcw_merge_create", "fmcw_merge_destroy", "fmcw_merge_enqueue",
                "fmcw_merge_set_grid_for_test")
@@ -146,23 +146,6 @@ def test_python_class(lib_built):
     u = (np.arange(8) - 4) / 8.0
     np.testing.assert_allclose(M.interp(p, u), [-0.5, -0.0625, 0.375])           # held at the ends
     np.testing.assert_allclose(M.interp(p, u, True, period=1.0), [0.46875, -0.0625, 0.46875])
-
-
-def random_list(seed, n_maps, nr, nd, density, dtype=DET_DTYPE, levels=5):
-    rng = np.random.default_rng(seed)
-    f, r, d = np.nonzero(rng.random((n_maps, nr, nd)) < density)
-    a = np.zeros(len(f), dtype)
-    a["frame"], a["range"], a["doppler"] = f, r, d
-    a["mag"] = rng.integers(1, levels + 1, len(f)).astype(np.float32)
-    return a
-
-
-def tile_edge_list(n):
-    """Exactly n records of 32 x 32 maps whose last record is in frame 3: merged as 2 scans x 3 beams,
-    maps 4 and 5 are empty."""
-    recs = thin_to(random_list(40, 4, 32, 32, 0.7), n, n)
-    assert len(recs) == n and recs["frame"][-1] == 3
-    return recs
 
 
 @pytest.mark.parametrize("n", TILE_EDGE_SIZES)

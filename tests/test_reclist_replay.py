@@ -25,15 +25,13 @@ import pytest
 import reclist_cases as RC
 from conftest import REPO
 from fmcw import DET_DTYPE, MPLOT_DTYPE, PLOT_DTYPE, VPLOT_DTYPE
-from merge_ref import assert_mplots_match, merge_ref
+from gpu_support import GUARD, SENTINEL
+from merge_ref import assert_mplots_match, merge_ref, random_list as merge_list, tile_edge_list
 from plots_ref import assert_plots_match, plots_ref
-from test_merge_host import random_list as merge_list, tile_edge_list
 from tile_edge import TILE_EDGE_SIZES
 from unfold_ref import Cfg, assert_vplots_equal, random_list as unfold_list, unfold_ref
 
 CHILD_TIMEOUT = 0.5
-SENTINEL = 0xA5
-GUARD = 0xA5A5A5A5
 PLOTS, MERGE, UNFOLD = 0, 1, 2
 OUT_DTYPE = {PLOTS: PLOT_DTYPE, MERGE: MPLOT_DTYPE, UNFOLD: VPLOT_DTYPE}
 

@@ -17,6 +17,10 @@ from dataclasses import dataclass
 
 import numpy as np
 
+import scenario_ref as S
+from fmcw import DET_DTYPE, synth
+from tile_edge import thin_to
+
 VPLOT_REF_DTYPE = np.dtype([("frame", "<u4"), ("range", "<u2"), ("doppler", "<u2"), ("mag", "<f4"),
                             ("v_fine", "<i4"), ("fold", "<i2"), ("n_hits", "u1"), ("hit_mask", "u1"),
                             ("sum_mag", "<f4"), ("pos", "<u2"), ("n_ties", "<u2"), ("src", "<u4")])
@@ -199,3 +203,60 @@ def random_list(seed, n_frames, nr, nd, n_recs, dtype, levels=5, targets=6, cfg:
     a = np.zeros(len(f), dtype)
     a["frame"], a["range"], a["doppler"], a["mag"] = f + frame0, r, d, grid[f, r, d]
     return a
+
+
+# ---- lists at the tile edges of the frame index ----
+TILE_EDGE_CFG = Cfg(n_range=64, n_doppler=32, v_max=3 * 32 * 8, step=3)   # K = 3, one stream
+
+
+def tile_edge_list(n):
+    """Exactly n records of 64 x 32 frames whose last record is in frame 3: unfolded as 6 scans (two
+    dwells), frames 4 and 5 are empty."""
+    recs = thin_to(random_list(41, 4, 64, 32, n + n // 4 + 64, DET_DTYPE, cfg=TILE_EDGE_CFG, targets=20), n, n)
+    assert len(recs) == n and recs["frame"][-1] == 3, (len(recs), n, int(recs["frame"][-1]))
+    return recs
+
+
+# ---- the scenario's fighter ----
+TRUTH_MPS = -synth.TAC_MACH_MPS
+F0_HZ = 1000.0
+# (qualifying dwells, those in which the fighter's report is within one out_unit of the truth)
+FIGHTER_FACT = {"sea-128x32": ([0, 6], [0, 6]), "sea-256x64": ([0, 6], [0])}
+
+
+def scenario_cfg(scene):
+    """K 3, step 1, the default tolerances and m_of, v_max 2 Nc 8, out_unit 8."""
+    return Cfg(n_range=scene.ns, n_doppler=scene.nc, step=1, v_max=2 * scene.nc * 8)
+
+
+def truth_fine(scene):
+    return 2.0 * TRUTH_MPS / synth.TAC_WAVELENGTH / (F0_HZ / scene.nc)
+
+
+def fighter_fact(scene, plots, vplots):
+    """(qualifying dwells, dwells in which the fact holds, the fighter's report per qualifying dwell).
+    A dwell qualifies when it touches no notch scan and each of its three scans holds a plot within one
+    bin of the lead fighter's truth cell.  The fighter's report is the one of the dwell's first scan
+    (pos 0) whose source plot is that scan's plot nearest the truth cell (largest mag among those within
+    one bin).  The fact: its v_fine is within one out_unit (8 fine units) of the truth."""
+    _, truth = S.scene_cubes(scene)
+    r, d = plots["range"].astype(np.int64), plots["doppler"].astype(np.int64)
+
+    def fighter_plot(s):
+        rb, db = truth[s][0]
+        dd = np.abs(d - db)
+        at = np.flatnonzero((plots["frame"] == s) & (np.abs(r - rb) <= 1) & (np.minimum(dd, scene.nc - dd) <= 1))
+        return int(at[np.argmax(plots["mag"][at])]) if len(at) else None
+    qualifying, holds, reports = [], [], {}
+    for j in range(n_dwells(scene.n_scans, 3, 1)):
+        scans = range(j, j + 3)
+        src = [fighter_plot(s) for s in scans]
+        if any(s in scene.notch for s in scans) or None in src:
+            continue
+        qualifying.append(j)
+        rep = vplots[(vplots["frame"] == j) & (vplots["src"] == src[0])]
+        assert len(rep) == 1 and int(rep["pos"][0]) == 0, (j, rep)
+        reports[j] = rep[0]
+        if abs(int(rep["v_fine"][0]) - truth_fine(scene)) <= 8:
+            holds.append(j)
+    return qualifying, holds, reports

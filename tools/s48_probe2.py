@@ -8,7 +8,7 @@ sys.path.insert(0, "oracle")
 sys.path.insert(0, "fpga-fmcw-radar-processor_amd")
 import fmcw_oracle as O
 from fmcw import RadarCore, synth
-from test_gpu_parity import to_complex
+from gpu_support import to_complex
 from conftest import rel_err
 
 ns, nc, nf = 8192, 1024, 4
