@@ -48,6 +48,7 @@ MERGE_STATUS_WORDS = 3   # FMCW_MERGE_STATUS_WORDS: status_dev = merged plots fo
 UNFOLD_STATUS_WORDS = 4  # FMCW_UNFOLD_STATUS_WORDS: status_dev = reports found, records not examined, out of range, tied
 EXCISE_ZERO, EXCISE_INTERP = 0, 1   # fmcw_excise_mode
 EXCISE_STATUS_WORDS = 4  # FMCW_EXCISE_STATUS_WORDS: status_dev = samples repaired, lines repaired, samples flagged, lines over half
+MIMO_ALIGN_NONE, MIMO_ALIGN_DFT = 0, 1   # fmcw_mimo_align
 BEARING_NO_ANGLE, BEARING_ONE_RX, BEARING_OUT_OF_RANGE = 1, 2, 4   # fmcw_bearing.flags bits
 
 STATUS_NAMES = {0: "FMCW_OK", -1: "FMCW_EINVAL", -2: "FMCW_ENOMEM", -3: "FMCW_EHIP",
@@ -157,6 +158,12 @@ class FmcwExciseConfig(C.Structure):
                 ("device_id", C.c_int32), ("reserved", C.c_uint32 * 2)]
 
 
+class FmcwMimoConfig(C.Structure):
+    _fields_ = [("n_range", C.c_uint32), ("n_chirps", C.c_uint32), ("n_rx", C.c_uint32),
+                ("n_tx", C.c_uint32), ("align", C.c_int32), ("reserved", C.c_uint32 * 2),
+                ("device_id", C.c_int32)]
+
+
 class FmcwCmapConfig(C.Structure):
     _fields_ = [("n_range", C.c_uint32), ("n_doppler", C.c_uint32), ("n_streams", C.c_uint32),
                 ("gain", C.c_float), ("alpha", C.c_float), ("floor", C.c_float), ("clip", C.c_float),
@@ -254,6 +261,11 @@ SIGNATURES = {
     "fmcw_excise_destroy": (_I, [_VP]),
     "fmcw_excise_enqueue": (_I, [_VP, _VP, _SZ, _VP, _VP, _VP, _VP, _VP]),
     "fmcw_excise_set_grid_for_test": (_I, [_VP, C.c_uint32]),
+    "fmcw_mimo_config_default": (None, [C.POINTER(FmcwMimoConfig)]),
+    "fmcw_mimo_create": (_I, [C.POINTER(FmcwMimoConfig), C.POINTER(_VP)]),
+    "fmcw_mimo_destroy": (_I, [_VP]),
+    "fmcw_mimo_enqueue": (_I, [_VP, _VP, _SZ, _VP, _VP]),
+    "fmcw_mimo_set_grid_for_test": (_I, [_VP, C.c_uint32]),
     "fmcw_cmap_config_default": (None, [C.POINTER(FmcwCmapConfig)]),
     "fmcw_cmap_create": (_I, [C.POINTER(FmcwCmapConfig), C.POINTER(_VP)]),
     "fmcw_cmap_destroy": (_I, [_VP]),

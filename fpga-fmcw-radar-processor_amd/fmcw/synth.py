@@ -63,6 +63,36 @@ def frames(n_frames: int, ns: int, nc: int, n_rx: int = 1, recipe: str = "two_ta
     return np.stack([frame(ns, nc, n_rx, recipe, seed + f, dtype, rx_phase) for f in range(n_frames)])
 
 
+def tdm_frames(n_frames: int, ns: int, n_chirps: int, n_rx: int, n_tx: int, recipe: str = "two_targets",
+               seed: int = 1234, rx_phase=0.25) -> np.ndarray:
+    """frames() as a time-division MIMO front end records it: complex64 [frame][rx][chirp][sample], chirp
+    c transmitted by TX c mod n_tx, the transmitters n_rx elements apart, so that receiver k sees the
+    element phase 2 pi rx_phase (k + n_rx (c mod n_tx)) on chirp c: a uniform line array of n_tx * n_rx
+    virtual elements.  The recipe's Doppler d stays in cycles per n_chirps chirps; one transmitter's n_d =
+    n_chirps / n_tx chirps see d mod n_d.  The targets and the noise are frames()'s draws (per-frame seed
+    = seed + frame): with n_tx = 1 the cube is frames()'s."""
+    if n_tx < 1 or n_chirps % n_tx:
+        raise ValueError(f"n_tx {n_tx}: n_chirps {n_chirps} must be a whole number of TX cycles")
+    n = np.arange(ns)[None, :]
+    c = np.arange(n_chirps)[:, None]
+    out = np.empty((n_frames, n_rx, n_chirps, ns), np.complex128)
+    for f in range(n_frames):
+        rng = np.random.Generator(np.random.PCG64(seed + f))
+        tg, noise = _targets(recipe, ns, n_chirps, rng)
+        ph = [float(rx_phase)] * len(tg) if np.ndim(rx_phase) == 0 else [float(p) for p in rx_phase]
+        if len(ph) != len(tg):
+            raise ValueError(f"rx_phase has {len(ph)} values for the {len(tg)} targets of {recipe}")
+        for rx in range(n_rx):
+            x = np.zeros((n_chirps, ns), np.complex128)
+            for (r, d, a), p in zip(tg, ph):
+                x += a * np.exp(2j * np.pi * (r * n / ns + d * c / n_chirps + p * (rx + n_rx * (c % n_tx))))
+            x += noise * (rng.uniform(-1, 1, (n_chirps, ns)) + 1j * rng.uniform(-1, 1, (n_chirps, ns)))
+            out[f, rx] = x
+    i = np.clip(np.rint(out.real), -32768, 32767)
+    q = np.clip(np.rint(out.imag), -32768, 32767)
+    return (i + 1j * q).astype(np.complex64)
+
+
 def interference_bursts(cube: np.ndarray, every: int, length: int, amplitude: float, seed: int, sweep: float = 0.002):
     """Mutual interference: another FMCW radar's chirp crossing ours.  In every `every`-th chirp (chirps
     0, every, 2 every, ...) of each frame and rx of `cube` -- complex [..., chirp, sample], or float16 /

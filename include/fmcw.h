@@ -109,7 +109,10 @@ extern "C" {
                                existing changes.
                                Still 8 with the interference exciser (fmcw_excise_*,
                                fmcw_excise_config): functions and types of its own, in front of
-                               fmcw_enqueue; nothing existing changes */
+                               fmcw_enqueue; nothing existing changes.
+                               Still 8 with the TDM-MIMO virtual array (fmcw_mimo_*, fmcw_mimo_config):
+                               functions and types of its own, between fmcw_range_ct and the objects
+                               that read its spectrum; nothing existing changes */
 
 typedef enum {
   FMCW_OK = 0,
@@ -1252,6 +1255,67 @@ int fmcw_excise_enqueue(fmcw_exciser* e, const void* cube_dev, size_t n_frames, 
  * a workgroup through several lines.  0 = the built-in bound (the workgroups resident at once), else
  * min(that bound, grid).  Results never depend on it. */
 int fmcw_excise_set_grid_for_test(fmcw_exciser* e, uint32_t grid);
+
+/* ---- TDM-MIMO virtual array: split the chirps by transmitter and time-align the TX slots ----
+ * A front end with n_tx transmitters that fire in turn, chirp by chirp, sees n_tx * n_rx virtual
+ * channels.  This stage sorts the chirps of fmcw_range_ct's spectrum by transmitter and writes a spectrum
+ * of n_tx * n_rx channels and n_d = n_chirps / n_tx chirps, which the bearing estimator, the beamformer
+ * and the adaptive weights read unchanged (n_rx' = n_tx * n_rx, n_doppler' = n_d).  The transmitters'
+ * chirps are taken at different times: a target's Doppler adds a phase step between the TX blocks of the
+ * raw de-interleaved array, which biases the bearing.  FMCW_MIMO_ALIGN_DFT removes it by delaying TX t's
+ * sequence by t / n_tx samples, so that every channel is sampled at TX 0's instants.  An object of its
+ * own, not part of fmcw_handle / fmcw_config; the reference (one transmitter) has no such stage.
+ *
+ * Input.   spec[f][k][r][c], complex fp32, exactly as fmcw_range_ct writes it for (n_range, n_chirps,
+ *          n_rx); n_chirps = n_tx * n_d.  Chirp c was transmitted by TX c mod n_tx: TX t fires in slot t.
+ *          Another firing order permutes the output blocks; that is the caller's business.
+ * Output.  out[f][v][r][m], complex fp32, v = t * n_rx + k, m = 0 .. n_d - 1: the layout of a
+ *          fmcw_range_ct spectrum for (n_range, n_d, n_tx * n_rx).  With a TX spacing of n_rx elements
+ *          the virtual array is the uniform line array the bearing estimator and steering weights assume.
+ * Steps.   u_t[m] = spec[f][k][r][m * n_tx + t].
+ *          FMCW_MIMO_ALIGN_NONE: out = u_t, a byte-exact copy.
+ *          FMCW_MIMO_ALIGN_DFT:  a band-limited circular delay of t / n_tx samples,
+ *            U_t[q]      = sum_m u_t[m] exp(-2 pi i q m / n_d)
+ *            out[..][m]  = (1 / n_d) sum_q U_t[q] exp(-2 pi i s(q) t / (n_tx n_d)) exp(+2 pi i q m / n_d)
+ *            s(q) = q for q < n_d / 2, q - n_d for q >= n_d / 2: the Nyquist bin takes the negative sign.
+ *          All arithmetic is fp32.
+ * Notes.   TX 0's channels are u_0 up to rounding; with n_tx = 1 the stage is a copy.
+ *          The alignment assumes |Doppler| below half the per-TX PRF.  A faster target aliases as it does
+ *          in any TDM radar; fmcw_unfold_* is the remedy.
+ *          The Doppler window and the MTI canceller are not applied here: the downstream objects apply
+ *          theirs.
+ *          n_tx is a power of two because fmcw_range_ct needs a power-of-two chirp count: n_tx = 3 is out
+ *          of scope. */
+typedef enum { FMCW_MIMO_ALIGN_NONE = 0, FMCW_MIMO_ALIGN_DFT = 1 } fmcw_mimo_align;
+typedef struct fmcw_mimo_config {   /* 32 bytes */
+  uint32_t n_range;            /* as fmcw_config: power of two, 64..8192 */
+  uint32_t n_chirps;           /* fmcw_range_ct's n_doppler: power of two, 32..1024 */
+  uint32_t n_rx;               /* 1..64; n_tx * n_rx <= 64, the channel limit of the downstream objects */
+  uint32_t n_tx;               /* power of two, 1..32; n_d = n_chirps / n_tx >= 32 */
+  int32_t align;               /* fmcw_mimo_align */
+  uint32_t reserved[2];        /* must be 0 */
+  int32_t device_id;           /* 0..63 */
+} fmcw_mimo_config;
+typedef struct fmcw_mimo fmcw_mimo;
+/* Defaults: 1024, 128 chirps, 4 rx, 2 tx, ALIGN_DFT, device 0. */
+void fmcw_mimo_config_default(fmcw_mimo_config* cfg);
+/* Validates every field before any device access (FMCW_EINVAL, the message names the field, *out is
+ * NULL), then FMCW_ENODEV as fmcw_excise_create.  A virtual array owns no device memory. */
+int fmcw_mimo_create(const fmcw_mimo_config* cfg, fmcw_mimo** out);
+int fmcw_mimo_destroy(fmcw_mimo* m);   /* NULL is FMCW_OK */
+/* Device pointers only; stream-ordered, allocates nothing, never synchronises and keeps no state
+ * between calls, so it can be captured into a hipGraph after fmcw_range_ct on the same stream and
+ * replayed.  One launch: every point is read once and written once.
+ * spec_dev: n_frames frames as fmcw_range_ct writes them for (n_range, n_chirps, n_rx), 16-byte aligned.
+ * out_dev:  n_frames frames of n_tx * n_rx x n_range x n_d complex fp32 (as many bytes as spec_dev),
+ *           16-byte aligned; it must not overlap spec_dev.  Nothing is stored beyond them.
+ * n_frames == 0 is FMCW_OK and launches nothing. */
+int fmcw_mimo_enqueue(fmcw_mimo* m, const void* spec_dev, size_t n_frames, void* out_dev, void* stream);
+/* Test hook: bounds the workgroups of the persistent kernel, whose waves stride over tiles of 1024
+ * points, so that a small call drives a workgroup through several tiles, channels and frames.  0 = the
+ * built-in bound (the workgroups resident at once), else min(that bound, grid).  Results never depend
+ * on it. */
+int fmcw_mimo_set_grid_for_test(fmcw_mimo* m, uint32_t grid);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
