@@ -19,7 +19,8 @@ from .cacfar import CaCfar  # noqa: F401
 from .cmap import ClutterMap  # noqa: F401
 from .excise import InterferenceExciser  # noqa: F401
 from .mimo import VirtualArray  # noqa: F401
+from .doa import AngleResolver, DOA_DTYPE, line_steering, planar_steering, calibrated  # noqa: F401
 from . import synth, formats  # noqa: F401
 
-__all__ = ["VirtualArray", "InterferenceExciser", "VelocityUnfolder", "VPLOT_DTYPE", "velocity_mps", "BeamMerger", "MPLOT_DTYPE", "AdaptiveWeights", "steering_vectors", "ADAPT_FALLBACK", "ClutterMap", "DeviceTwsTracker", "CaCfar", "BeamFormer", "steering_weights", "BearingEstimator", "BEARING_DTYPE", "PlotExtractor", "PLOT_DTYPE", "RadarCore", "RadarOutput", "DeviceBuffer", "DET_DTYPE", "FmcwError", "load",
+__all__ = ["AngleResolver", "DOA_DTYPE", "line_steering", "planar_steering", "calibrated", "VirtualArray", "InterferenceExciser", "VelocityUnfolder", "VPLOT_DTYPE", "velocity_mps", "BeamMerger", "MPLOT_DTYPE", "AdaptiveWeights", "steering_vectors", "ADAPT_FALLBACK", "ClutterMap", "DeviceTwsTracker", "CaCfar", "BeamFormer", "steering_weights", "BearingEstimator", "BEARING_DTYPE", "PlotExtractor", "PLOT_DTYPE", "RadarCore", "RadarOutput", "DeviceBuffer", "DET_DTYPE", "FmcwError", "load",
            "device_count", "magnitude", "TwsTracker", "TRACK_DTYPE", "synth", "formats", "pack_adc_words", "adc_words_to_cube"]

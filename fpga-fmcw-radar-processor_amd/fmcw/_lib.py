@@ -50,6 +50,9 @@ EXCISE_ZERO, EXCISE_INTERP = 0, 1   # fmcw_excise_mode
 EXCISE_STATUS_WORDS = 4  # FMCW_EXCISE_STATUS_WORDS: status_dev = samples repaired, lines repaired, samples flagged, lines over half
 MIMO_ALIGN_NONE, MIMO_ALIGN_DFT = 0, 1   # fmcw_mimo_align
 BEARING_NO_ANGLE, BEARING_ONE_RX, BEARING_OUT_OF_RANGE = 1, 2, 4   # fmcw_bearing.flags bits
+DOA_NO_SNAPSHOT, DOA_ONE_CH = 1, 2   # fmcw_doa.flags bits
+DOA_MAX_SRC = 4           # FMCW_DOA_MAX_SRC: sources per fmcw_doa record
+DOA_STATUS_WORDS = 2      # FMCW_DOA_STATUS_WORDS: n_out_dev = records processed, without a snapshot
 
 STATUS_NAMES = {0: "FMCW_OK", -1: "FMCW_EINVAL", -2: "FMCW_ENOMEM", -3: "FMCW_EHIP",
                 -4: "FMCW_EDETCAP", -5: "FMCW_ENODEV"}
@@ -164,6 +167,22 @@ class FmcwMimoConfig(C.Structure):
                 ("device_id", C.c_int32)]
 
 
+class FmcwDoaSrc(C.Structure):
+    _fields_ = [("grid", C.c_uint32), ("pos", C.c_float), ("amp_re", C.c_float), ("amp_im", C.c_float)]
+
+
+class FmcwDoa(C.Structure):
+    _fields_ = [("frame", C.c_uint32), ("range", C.c_uint16), ("doppler", C.c_uint16),
+                ("flags", C.c_uint32), ("n_src", C.c_uint32), ("total", C.c_float),
+                ("residual", C.c_float), ("reserved", C.c_uint32 * 2), ("src", FmcwDoaSrc * 4)]
+
+
+class FmcwDoaConfig(C.Structure):
+    _fields_ = [("n_ch", C.c_uint32), ("n_grid", C.c_uint32), ("k_max", C.c_uint32),
+                ("relax_passes", C.c_uint32), ("min_rel", C.c_float), ("refine", C.c_uint32),
+                ("max_records", C.c_uint32), ("device_id", C.c_int32)]
+
+
 class FmcwCmapConfig(C.Structure):
     _fields_ = [("n_range", C.c_uint32), ("n_doppler", C.c_uint32), ("n_streams", C.c_uint32),
                 ("gain", C.c_float), ("alpha", C.c_float), ("floor", C.c_float), ("clip", C.c_float),
@@ -266,6 +285,13 @@ SIGNATURES = {
     "fmcw_mimo_destroy": (_I, [_VP]),
     "fmcw_mimo_enqueue": (_I, [_VP, _VP, _SZ, _VP, _VP]),
     "fmcw_mimo_set_grid_for_test": (_I, [_VP, C.c_uint32]),
+    "fmcw_doa_config_default": (None, [C.POINTER(FmcwDoaConfig)]),
+    "fmcw_doa_create": (_I, [C.POINTER(FmcwDoaConfig), C.POINTER(_VP)]),
+    "fmcw_doa_destroy": (_I, [_VP]),
+    "fmcw_doa_set_steering": (_I, [_VP, _VP, _VP]),
+    "fmcw_doa_set_steering_dev": (_I, [_VP, _VP, _VP]),
+    "fmcw_doa_enqueue": (_I, [_VP, _VP, _VP, _SZ, _SZ, _VP, _VP, _VP, _VP, _VP]),
+    "fmcw_doa_set_grid_for_test": (_I, [_VP, C.c_uint32]),
     "fmcw_cmap_config_default": (None, [C.POINTER(FmcwCmapConfig)]),
     "fmcw_cmap_create": (_I, [C.POINTER(FmcwCmapConfig), C.POINTER(_VP)]),
     "fmcw_cmap_destroy": (_I, [_VP]),

@@ -93,6 +93,35 @@ def tdm_frames(n_frames: int, ns: int, n_chirps: int, n_rx: int, n_tx: int, reci
     return (i + 1j * q).astype(np.complex64)
 
 
+def two_in_cell_frames(n_frames: int, ns: int, n_chirps: int, n_rx: int, n_tx: int, cell=(20, 5),
+                       rx_phase=(0.10, 0.22), amps=(8000.0, 5600.0), noise: float = 20.0, seed: int = 1234) -> np.ndarray:
+    """tdm_frames() with the targets given, all in one range-Doppler cell: complex64 [frame][rx][chirp]
+    [sample], every target at range bin cell[0] and at Doppler cell[1] cycles per n_chirps chirps (an
+    integer, so that one transmitter's n_chirps / n_tx chirps see bin cell[1] too), target q at rx_phase[q]
+    cycles per element of the n_tx * n_rx virtual line array with amplitude amps[q] and a phase of its own
+    (drawn per frame).  The bearing estimator reads one blended bearing there; the angle resolver reads
+    them apart.  Uniform noise of +-noise per component, per-frame seed = seed + frame."""
+    if n_tx < 1 or n_chirps % n_tx:
+        raise ValueError(f"n_tx {n_tx}: n_chirps {n_chirps} must be a whole number of TX cycles")
+    if len(rx_phase) != len(amps):
+        raise ValueError(f"{len(rx_phase)} bearings for {len(amps)} amplitudes")
+    n = np.arange(ns)[None, :]
+    c = np.arange(n_chirps)[:, None]
+    out = np.empty((n_frames, n_rx, n_chirps, ns), np.complex128)
+    for f in range(n_frames):
+        rng = np.random.Generator(np.random.PCG64(seed + f))
+        phi = rng.uniform(0.0, 1.0, len(amps))
+        for rx in range(n_rx):
+            x = np.zeros((n_chirps, ns), np.complex128)
+            for a, p, ph in zip(amps, rx_phase, phi):
+                x += a * np.exp(2j * np.pi * (cell[0] * n / ns + cell[1] * c / n_chirps + p * (rx + n_rx * (c % n_tx)) + ph))
+            x += noise * (rng.uniform(-1, 1, (n_chirps, ns)) + 1j * rng.uniform(-1, 1, (n_chirps, ns)))
+            out[f, rx] = x
+    i = np.clip(np.rint(out.real), -32768, 32767)
+    q = np.clip(np.rint(out.imag), -32768, 32767)
+    return (i + 1j * q).astype(np.complex64)
+
+
 def interference_bursts(cube: np.ndarray, every: int, length: int, amplitude: float, seed: int, sweep: float = 0.002):
     """Mutual interference: another FMCW radar's chirp crossing ours.  In every `every`-th chirp (chirps
     0, every, 2 every, ...) of each frame and rx of `cube` -- complex [..., chirp, sample], or float16 /

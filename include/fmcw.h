@@ -112,7 +112,10 @@ extern "C" {
                                fmcw_enqueue; nothing existing changes.
                                Still 8 with the TDM-MIMO virtual array (fmcw_mimo_*, fmcw_mimo_config):
                                functions and types of its own, between fmcw_range_ct and the objects
-                               that read its spectrum; nothing existing changes */
+                               that read its spectrum; nothing existing changes.
+                               Still 8 with the angle resolver (fmcw_doa_*, fmcw_doa, fmcw_doa_config):
+                               functions and types of its own, behind fmcw_bearings_enqueue; nothing
+                               existing changes */
 
 typedef enum {
   FMCW_OK = 0,
@@ -669,7 +672,8 @@ int fmcw_unfold_set_grid_for_test(fmcw_unfolder* u, uint32_t grid);
  *   coherence = |P| / sum_{k=0}^{n_rx-2} |s_{k+1}| |s_k|   1 for one plane wave, lower when two
  *                                targets share the cell; 0 if the denominator is 0 or not finite
  * The closed-form phase comparison, not a scan over an angle grid: O(n_rx), and no argmax to differ
- * between precisions.  Callers who want more (MUSIC, a Bartlett scan) take the snapshots. */
+ * between precisions.  Callers who want more (MUSIC, a Bartlett scan) take the snapshots; the scan
+ * over a steering table with successive cancellation is fmcw_doa_* below. */
 #define FMCW_BEARING_NO_ANGLE 1u      /* |sin_theta| > 1: no real angle */
 #define FMCW_BEARING_ONE_RX 2u        /* n_rx == 1: nu = 0, sin_theta = 0, coherence = 0 */
 #define FMCW_BEARING_OUT_OF_RANGE 4u  /* frame >= n_frames of the call, range >= n_range or doppler >=
@@ -1316,6 +1320,105 @@ int fmcw_mimo_enqueue(fmcw_mimo* m, const void* spec_dev, size_t n_frames, void*
  * built-in bound (the workgroups resident at once), else min(that bound, grid).  Results never depend
  * on it. */
 int fmcw_mimo_set_grid_for_test(fmcw_mimo* m, uint32_t grid);
+
+/* ---- Angle resolution: several sources per detection from its channel snapshot ------------
+ * fmcw_bearings_* reads one plane wave on a uniform line array.  Two targets in one range-Doppler cell
+ * give it one blended bearing, and it cannot use a planar or thinned array or a calibration table.  The
+ * resolver scans each record's snapshot (the snaps_dev of fmcw_bearings_enqueue) over a caller-supplied
+ * steering table, takes the strongest grid point, cancels it and scans again (matching pursuit), then
+ * re-estimates every source against the others (RELAX).  An object of its own, not part of fmcw_handle
+ * / fmcw_config; the reference (one receive channel) has no such stage.
+ *
+ * Steering table.  A[g][k], complex fp32, g = 0 .. n_grid - 1 rows of n_ch entries: the array's response
+ *   to a unit source at grid point g, geometry and calibration folded in by the caller.  The object keeps
+ *   w[g] = 1 / sum_k |A[g][k]|^2, computed in fp64 and stored as fp32.  fmcw_doa_set_steering rejects a
+ *   row whose norm is 0 or not finite; fmcw_doa_set_steering_dev gives such a row w[g] = 0 and reads it as
+ *   zeros, so it can never win.  Until a table is set every w[g] is 0.
+ *
+ * Per record i, s[k] = snaps_dev[i * n_ch + k], r_0 = s:
+ *   Stage j = 0 .. k_max - 1:
+ *     y_j[g] = sum_k conj(A[g][k]) r_j[k]
+ *     B_j[g] = |y_j[g]|^2 w[g]
+ *     g_j    = the lowest g at which B_j is largest
+ *     the search ends if B_j[g_j] == 0, and for j > 0 if B_j[g_j] < min_rel * B_0[g_0]
+ *     a_j = y_j[g_j] w[g_j];   r_{j+1} = r_j - a_j A[g_j][:]
+ *   Then relax_passes passes, each over the sources found, in order of discovery: a_j A[g_j][:] is added
+ *   back to the residual, g_j and a_j are taken anew from a scan of that residual (the same argmax and
+ *   amplitude, no end test), and the new a_j A[g_j][:] is subtracted.
+ *   Position.  With refine = 1, on the B of the scan that fixed the source's final g = g_j:
+ *     off = 0.5 (B[g-1] - B[g+1]) / (B[g-1] - 2 B[g] + B[g+1]),
+ *     off = 0 if that denominator is not negative, or at g = 0 or g = n_grid - 1;  pos = g + off.
+ *   With refine = 0, pos = g: for 2-D grids, whose neighbouring indices are not neighbouring angles.
+ *   All arithmetic is fp32. */
+#define FMCW_DOA_NO_SNAPSHOT 1u   /* the snapshot is all zeros or has a value that is not finite: n_src = 0,
+                                     nothing is scanned, total = residual = 0, a spectrum row of zeros */
+#define FMCW_DOA_ONE_CH 2u        /* n_ch == 1 */
+#define FMCW_DOA_MAX_SRC 4
+typedef struct fmcw_doa_src {  /* 16 bytes */
+  uint32_t grid;               /* g_j */
+  float pos;                   /* g_j + off */
+  float amp_re, amp_im;        /* a_j */
+} fmcw_doa_src;
+typedef struct fmcw_doa {      /* 96 bytes */
+  uint32_t frame;              /* the record's cell, copied from cells_dev (zero without it) */
+  uint16_t range;
+  uint16_t doppler;
+  uint32_t flags;              /* FMCW_DOA_* bits */
+  uint32_t n_src;              /* sources found, 0 .. k_max */
+  float total;                 /* sum_k |s[k]|^2 */
+  float residual;              /* sum_k |r[k]|^2 after the last subtraction */
+  uint32_t reserved[2];        /* written as 0 */
+  fmcw_doa_src src[FMCW_DOA_MAX_SRC];   /* in order of discovery; zeros from n_src on */
+} fmcw_doa;
+typedef struct fmcw_doa_config {   /* 32 bytes */
+  uint32_t n_ch;               /* channels of a snapshot, 1..64 */
+  uint32_t n_grid;             /* rows of the steering table: a multiple of 64, 64..1024 */
+  uint32_t k_max;              /* most sources per record, 1..4 */
+  uint32_t relax_passes;       /* 0..3 */
+  float min_rel;               /* in [0, 1): a later source must reach this share of B_0[g_0] */
+  uint32_t refine;             /* 0 or 1 */
+  uint32_t max_records;        /* most records one call processes, 1..2^31-1 (no scratch depends on it) */
+                               /* device memory of a resolver: 16 B x n_ch x n_grid + 4 B x n_grid + 8 KiB */
+  int32_t device_id;           /* 0..63 */
+} fmcw_doa_config;
+typedef struct fmcw_doa_resolver fmcw_doa_resolver;
+/* Status words of fmcw_doa_enqueue (n_out_dev). */
+#define FMCW_DOA_STATUS_WORDS 2
+/* Defaults: 16 channels, 256 grid points, k_max 2, 2 passes, min_rel 0.02, refine 1, max_records 2^20,
+ * device 0. */
+void fmcw_doa_config_default(fmcw_doa_config* cfg);
+/* Validates before any device access (FMCW_EINVAL, the message names the field, *out is NULL), then
+ * FMCW_ENODEV / FMCW_ENOMEM as fmcw_bearings_create.  The table starts as zeros. */
+int fmcw_doa_create(const fmcw_doa_config* cfg, fmcw_doa_resolver** out);
+int fmcw_doa_destroy(fmcw_doa_resolver* d);   /* NULL is FMCW_OK */
+/* The steering table from the host: steering_host holds n_grid x n_ch complex fp32 (re, im pairs), row
+ * g first.  A row whose norm is 0 or not finite is FMCW_EINVAL (the message names the row) and leaves the
+ * object's table as it was.  The upload and the conversion run on `stream`, ordered with the calls enqueued
+ * on it before and after; the function returns once steering_host has been read (it waits for `stream`). */
+int fmcw_doa_set_steering(fmcw_doa_resolver* d, const float* steering_host, void* stream);
+/* The same from device memory (8-byte aligned, the same layout), stream-ordered and capturable: the table
+ * need not leave the device.  No row is rejected: see "Steering table" above. */
+int fmcw_doa_set_steering_dev(fmcw_doa_resolver* d, const void* steering_dev, void* stream);
+/* Device pointers only; stream-ordered, allocates nothing, never synchronises and keeps no state
+ * between calls, so it can be captured into a hipGraph after fmcw_bearings_enqueue on the same stream
+ * and replayed.  One stream at a time per resolver (its 8 KiB of per-workgroup counts are shared by its
+ * calls).
+ * snaps_dev: rec_cap snapshots of n_ch complex fp32, 8-byte aligned: fmcw_bearings_enqueue's snaps_dev.
+ * cells_dev: NULL, or rec_cap records of cell_stride bytes (16 or 32, else FMCW_EINVAL; 4-byte aligned)
+ *            that begin with {uint32 frame; uint16 range; uint16 doppler}: fmcw_bearing, fmcw_det, fmcw_plot.
+ * Processes n = min(n_records_dev[0], rec_cap, max_records) records (n is read on the device):
+ *   doa_dev[i], i < n (16-byte aligned, room for min(rec_cap, max_records) records); nothing is stored
+ *                  beyond them,
+ *   spectrum_dev[i * n_grid + g] = B_0[g] as fp32 (4-byte aligned), unless spectrum_dev is NULL,
+ *   n_out_dev[0] = n, n_out_dev[1] = the records with FMCW_DOA_NO_SNAPSHOT among them.
+ * With n = 0 it writes {0, 0} and touches nothing else. */
+int fmcw_doa_enqueue(fmcw_doa_resolver* d, const void* snaps_dev, const void* cells_dev, size_t cell_stride,
+                     size_t rec_cap, const uint32_t* n_records_dev, fmcw_doa* doa_dev, float* spectrum_dev,
+                     uint32_t* n_out_dev, void* stream);
+/* Test hook: bounds the workgroups of the resolver's kernel, whose waves stride over the records, so
+ * that a short list drives a workgroup through several records.  0 = the built-in bound (2048), else
+ * min(that bound, grid).  Results never depend on it. */
+int fmcw_doa_set_grid_for_test(fmcw_doa_resolver* d, uint32_t grid);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
