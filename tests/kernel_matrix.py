@@ -29,6 +29,10 @@ depends on the CU count and has no key; one case per Doppler size and window run
 The persistent loops of K1, K2, k_cfar1d and K3 run one iteration per workgroup at these shapes; the
 cases "*-loop-g<grid>" repeat a case of the table under capped grids (Case.grid, fmcw_set_param's
 FMCW_PARAM_GRID_*) and claim a "<key>/loop" twin only where `loops` counts three iterations or more.
+
+`WHITE` is a derived table: for every K1 / K2 key with a twin, the twin, and the AMBM branch, the first
+whole-path case of `CASES` that claims it, once more on white full-scale noise ("<id>-white"), where
+`check_every_cell` holds every cell of the map to 1e-4 of the rms of its own range row.
 """
 from __future__ import annotations
 
@@ -1412,3 +1416,133 @@ def check_case_map(c: Cfg, got, ref):
             assert e <= 2e-3, f"frame {f}: max rel err {e:.3g}"
     else:
         check_map(got, ref)
+
+
+# ---- the white scene: every cell of the K1 -> K2 map checked -----------------------------------
+# check_map holds the map to 1e-4 of the frame's peak, and per bin only above 1e-3 of that peak; on
+# `random_target` / `two_targets` (one or two tones over weak noise) that leaves nearly every cell
+# outside the targets' rows unchecked (test_kernel_matrix.test_tone_scene_leaves_most_cells_unchecked).
+# The cases "<base id>-white" run the configuration, frames, grid and chunking of a case above on
+# recipe "uniform" (make_cube: white full-scale noise), where every range row of the map is at full
+# scale, under check_every_cell: 1e-4 of the rms of the cell's own range row.
+WHITE_TOL = 1e-4          # gpu_support.MAP_TOL, applied to the row's scale instead of the frame's peak
+WHITE_SEED = 20000
+WHITE_CAP = 0.02          # the largest share of cells in which a wrong map may pass: fp32 and S48 spectrum
+WHITE_CAP_F16 = 0.25      # fp16 spectrum, whose rule carries the format's worst-case bound
+
+
+def _white_admissible(case: Case) -> bool:
+    """Whole-path cases that can have a white twin: not the Q15 window, not the integer datapath (its
+    references are built on the GPU's own spectrum, and a full-scale input would clip everywhere)."""
+    return (case.group == "process" and case.cfg.window != "q15_rtl"
+            and case.recipe not in ("int_clean", "int_sat"))
+
+
+def _white_cfg(case: Case) -> Cfg:
+    """A dB case runs with the linear map: the dB map as such is test_whole_path's."""
+    return dataclasses.replace(case.cfg, map_kind="linear") if case.cfg.map_kind == "db" else case.cfg
+
+
+def white_wanted(key: str) -> bool:
+    """K1 / K2 keys that loopable() accepts, and their "/loop" twins; and the generic K2's AMBM branch,
+    which has no twin but computes another map (check_every_cell has a rule of its own for it)."""
+    base = key[:-5] if key.endswith("/loop") else key
+    table = reachable_with_symbols()
+    if base not in table or not base.startswith(("k_range", "k_doppler")):
+        return False
+    return loopable(base, table[base]) or key.endswith("/ambm")
+
+
+def white_targets() -> set:
+    """The keys a white twin can exist for: every wanted key of reachable() that some admissible
+    whole-path case of CASES claims (a dB case with its linear map)."""
+    claimed = set()
+    for b in CASES:
+        if _white_admissible(b):
+            claimed |= dataclasses.replace(b, cfg=_white_cfg(b)).keys()
+    return {k for k in reachable() if white_wanted(k)} & claimed
+
+
+def _build_white():
+    todo = white_targets()
+    out = []
+    for linear_first in (True, False):      # a dB case only for what no linear case claims
+        for b in CASES:
+            if not _white_admissible(b) or (b.cfg.map_kind == "db") == linear_first:
+                continue
+            w = dataclasses.replace(b, id=b.id + "-white", cfg=_white_cfg(b), recipe="uniform",
+                                    seed=WHITE_SEED + len(out))
+            mine = w.keys() & todo
+            if mine:
+                todo -= mine
+                out.append(w)
+                WHITE_BASE[w.id] = b.id
+    assert not todo, sorted(todo)
+    return tuple(out)
+
+
+WHITE_BASE = {}         # id of a white case -> id of the case whose configuration it runs
+WHITE = _build_white()
+
+
+def row_rms(ref):
+    """R[frame][range] = sqrt(mean_d ref[frame][range][d]^2)."""
+    return np.sqrt(np.mean(np.square(ref, dtype=np.float64), axis=-1))
+
+
+def every_cell_bound(c: Cfg, ref, case: Case):
+    """[frame][range]: how far a cell of that range row may lie from the fp64 oracle's.  1e-4 of the
+    row's rms; on the fp16 spectrum plus the format's bound fp16_row_error (which holds AMBM's two
+    floor steps already); AMBM on the other spectra plus those 2 steps, as test_integer_path adds them."""
+    bound = WHITE_TOL * row_rms(ref)
+    if c.spectrum == "f16":
+        bound = bound + fp16_row_error(case)
+    elif c.magnitude == "ambm":
+        bound = bound + 2.0
+    return bound
+
+
+def check_every_cell(c: Cfg, got, ref, case: Case):
+    """The map rule of a white case: every cell of `got` (finite float32 [frame][range][doppler]) within
+    every_cell_bound of `ref`, the fp64 oracle map of reference(case).  `c` is the configuration whose rule
+    applies (the case's own, or its fp32-spectrum form for an fp32 restatement).  Prints and returns the
+    worst fraction of the bound used."""
+    got = np.asarray(got)
+    assert got.dtype == np.float32 and got.shape == ref.shape, f"{case.id}: got {got.dtype} {got.shape}, reference {ref.shape}"
+    assert np.isfinite(got).all(), f"{case.id}: {int((~np.isfinite(got)).sum())} cells are not finite"
+    used = np.abs(got.astype(np.float64) - ref) / every_cell_bound(c, ref, case)[..., None]
+    worst = float(used.max())
+    print(f"{case.id}: worst fraction of the every-cell bound used {worst:.3g}")
+    if worst > 1.0:
+        f, r, d = np.unravel_index(int(used.argmax()), used.shape)
+        raise AssertionError(f"{case.id}: {int((used > 1.0).sum())} of {used.size} cells beyond the bound, the worst at frame {f} "
+                             f"range {r} doppler {d}: got {got[f, r, d]:.9g}, reference {ref[f, r, d]:.9g}, "
+                             f"{worst:.3g} of the bound")
+    return worst
+
+
+def unchecked_shares_map(ref, bound):
+    """The share of cells in which another map passes the every-cell rule (`bound` [frame][range]) against
+    `ref` [frame][range][doppler]: zeros, the reference rolled by one range row, by one Doppler bin, and the
+    previous frame's map (1.0 by construction where there is one frame)."""
+    def share(other):
+        return float((np.abs(other - ref) <= bound[..., None]).mean())
+    return {"zero": share(np.zeros_like(ref)), "row": share(np.roll(ref, 1, axis=1)),
+            "bin": share(np.roll(ref, 1, axis=2)),
+            "frame": share(np.roll(ref, 1, axis=0)) if ref.shape[0] > 1 else 1.0}
+
+
+def unchecked_shares_check_map(ref, fp16=False):
+    """The same four shares under the rule of the tone cases (check_case_map): a cell passes where the
+    other map is within 1e-4 (fp16 spectrum: 2e-3) of the frame's peak and, on the fp32 and S48 spectra,
+    within 1e-4 of the cell itself if the cell is above 1e-3 of that peak."""
+    peak = np.abs(ref).max(axis=(1, 2), keepdims=True)
+
+    def share(other):
+        err = np.abs(other - ref)
+        if fp16:
+            return float((err <= 2e-3 * peak).mean())
+        return float(((err <= WHITE_TOL * peak) & ((np.abs(ref) < 1e-3 * peak) | (err <= WHITE_TOL * np.abs(ref)))).mean())
+    return {"zero": share(np.zeros_like(ref)), "row": share(np.roll(ref, 1, axis=1)),
+            "bin": share(np.roll(ref, 1, axis=2)),
+            "frame": share(np.roll(ref, 1, axis=0)) if ref.shape[0] > 1 else 1.0}

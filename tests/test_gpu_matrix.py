@@ -21,6 +21,10 @@ prefetch, the LDS reuse behind the loop head's barrier, the counters over iterat
 what the last strip left.  Same oracle, same bounds; then the same handle once more with the caps
 at 0: map, spectrum, records and status words must be the same bytes (fmcw.h: results never depend
 on tuning parameters).
+The white scene (test_whole_path_every_cell, cases "*-white", kernel_matrix.WHITE): the tone scenes
+above leave nearly every cell outside the targets' rows below what check_map looks at.  Every K1 / K2
+key, "/loop" twins included, runs once more on white full-scale noise, where each cell is held to 1e-4
+of the rms of its own range row (kernel_matrix.check_every_cell), into sentinel-filled guarded buffers.
 tests/test_kernel_matrix.py shows on the CPU that the table covers the dispatch rules and that a
 correct fp32 implementation passes every case that the C restatement can run.
 """
@@ -34,7 +38,7 @@ import fmcw_oracle as O
 import kernel_matrix as K
 from conftest import rel_err
 from fmcw import DET_DTYPE, DeviceBuffer, RadarCore
-from gpu_support import check_map, run_cfar_stage, run_range_ct
+from gpu_support import Guarded, assert_all_written, check_map, run_cfar_stage, run_range_ct
 
 pytestmark = pytest.mark.gpu
 
@@ -366,3 +370,54 @@ def test_cfar2d_stage(gpu, case):
     print(f"{case.id}: {len(want)} detections")
     assert len(want) > 0
     np.testing.assert_array_equal(got, want)
+
+
+def _enqueue_guarded(core, cube_dev, case, bufs):
+    """One fmcw_enqueue into the sentinel-filled (map, records, status words) buffers: (map bytes as
+    float32, records, status words), after checking the three tails."""
+    c = case.cfg
+    dmap, ddets, dn = bufs
+    for b in bufs:
+        b.fill()
+    cap = ddets.nbytes // 16
+    core.enqueue(cube_dev, case.nf, dmap.ptr, ddets.ptr, cap, dn.ptr)
+    words = dn.get(np.uint32, (4,))          # a synchronous copy: behind the stream's work
+    for b in bufs:
+        b.check()
+    assert words[0] <= cap and words[1] == 0, (words.tolist(), cap)
+    return (dmap.get(np.float32, (case.nf, c.n_range, c.n_doppler)), ddets.get(DET_DTYPE, (int(words[0]),)),
+            [int(w) for w in words])
+
+
+@pytest.mark.parametrize("case", K.WHITE, ids=lambda c: c.id)
+def test_whole_path_every_cell(gpu, case):
+    """fmcw_enqueue on white full-scale noise, map, records and status words in guarded buffers filled
+    with the sentinel: the tails intact, every map word written, every cell within 1e-4 of the rms of its
+    range row of the fp64 oracle (kernel_matrix.check_every_cell: plus the format's bound on the fp16
+    spectrum, plus AMBM's two floor steps), the records those of the oracle CFAR on the GPU's own map
+    with nothing lost.  Under a capped grid, the same bytes once more with the caps at 0."""
+    c = case.cfg
+    cube, ref = K.reference(case)
+    cells = case.nf * c.n_range * c.n_doppler
+    over = dict(chunk_frames=case.chunk_frames) if case.chunk_frames else {}
+    din = DeviceBuffer(cube.nbytes)
+    bufs = (Guarded(cells * 4), Guarded(cells * 16), Guarded(16))
+    try:
+        din.upload(cube)
+        with make_core(c, case.nf, **over) as core:
+            created = cap_grids(core, case)
+            got, dets, words = _enqueue_guarded(core, din, case, bufs)
+            assert core.info("range_kernel") == K.range_family(c)
+            if created:
+                uncap_grids(core, created)
+                got0, dets0, words0 = _enqueue_guarded(core, din, case, bufs)
+                same_bytes(got0, got)
+                same_bytes(dets0, dets)
+                assert words0 == words
+    finally:
+        for b in bufs + (din,):
+            b.free()
+    assert_all_written(got, f"{case.id}: the map")
+    K.check_every_cell(c, got, ref, case)
+    np.testing.assert_array_equal(dets, K.oracle_dets(got, c))
+    assert words[2] == 0 and words[3] == 0        # no integer window, no 16-bit words on this datapath
